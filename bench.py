@@ -30,6 +30,12 @@ visible devices) and tracks its own streams (weak scaling, no data-path
 collective); the gloo group carries the barriers, the max-over-ranks time and
 the per-rank parity reports.
 
+A plain run times the headline workload only; the other configs' legs, the
+ingress leg, the parity replay, the CPU baselines, the sweeps, the isolated
+steps and the LSD floors described above run with `--full`.
+`--dump-outputs DIR` writes the timed tracker's last-step outputs as
+DIR/<name>.npy (tracker_outputs).
+
 Prints ONE JSON line (rank 0). See DESIGN.md §5 for the roofline accounting.
 """
 import argparse
@@ -132,12 +138,54 @@ def _render(args):
     return g, d
 
 
-def render_loop(n, seed, workers, cam_name="TUM1", stereo=False, cams=1):
+LOOP_CACHE = ROOT / ".bench_cache"   # rendered loops, written by `bench.py --prepare` only
+
+
+def loop_cache_file(n, seed, cam_name, stereo, cams):
+    """The cache file of one rendered loop: named by its arguments, the
+    renderer's source and the numpy version, so a stale file is never read."""
+    import hashlib
+    from _pkg import load_pkg
+    load_pkg()
+    import orbpl.synth as synth
+    key = repr((n, seed, cam_name, bool(stereo), cams, np.__version__)).encode()
+    tag = hashlib.sha256(Path(synth.__file__).read_bytes() + key).hexdigest()[:16]
+    return LOOP_CACHE / f"loop_{cam_name}_{n}_{seed}_{tag}.npz"
+
+
+def render_loop(n, seed, workers, cam_name="TUM1", stereo=False, cams=1, store=False):
     """(gray, depth) of an n-frame loop ([frame][camera] for a rig), or
-    (left, right) for stereo."""
+    (left, right) for stereo. A loop that `--prepare` rendered before is read
+    from LOOP_CACHE (the same arrays, bit for bit); store=True writes it."""
+    f = loop_cache_file(n, seed, cam_name, stereo, cams)
+    if f.exists():
+        with np.load(f) as d:
+            return d["a"], d["b"]
     with ProcessPoolExecutor(max_workers=workers) as ex:
         out = list(ex.map(_render, [(e, n, seed, cam_name, stereo, cams) for e in range(n * cams)]))
-    return np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
+    a, b = np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
+    if store:
+        f.parent.mkdir(parents=True, exist_ok=True)
+        tmp = f.with_name(f"{f.stem}.{os.getpid()}.tmp.npz")
+        np.savez(tmp, a=a, b=b)
+        os.replace(tmp, f)
+    return a, b
+
+
+def prepare(args):
+    """`--prepare` (run by __graft_entry__.build(), no GPU): render the loops a
+    plain one-GPU run of these arguments reads - the headline workload's and
+    the vocabulary's training frames - into LOOP_CACHE, so that the run itself
+    spends its set-up on the GPU work and not on ~1.5 CPU-seconds per frame."""
+    wl = WORKLOADS[args.workload]
+    cams = wl.get("cams", 1)
+    workers = min(16, os.cpu_count() or 4)
+    loops = [(args.loop if cams == 1 else args.rig_loop, 1, wl["cam"], wl["stereo"], cams)]
+    if args.bow:
+        loops.append((6, 100, "TUM1", False, 1))
+    for n, seed, cam_name, stereo, c in loops:
+        if not loop_cache_file(n, seed, cam_name, stereo, c).exists():
+            render_loop(n, seed, workers, cam_name, stereo, c, store=True)
 
 
 def level_areas(w=W, h=H, orb=ORB):
@@ -427,6 +475,63 @@ def compact_line(out, detail):
     return c
 
 
+DUMP_STREAMS = 32    # streams whose last frame --dump-outputs writes in full
+DUMP_MAX_BYTES = 64 << 20
+
+
+def tracker_outputs(tr, st, with_local):
+    """What a caller of the timed path holds after its last step, as float
+    arrays (--dump-outputs): every stream's pose Tcw and per-stream counts
+    (state, status, TrackLocalMap counts), and the last frame (undistorted
+    keypoints, descriptors, matches, outlier flags; KeyLines with lines) of a
+    fixed seeded sample of DUMP_STREAMS streams, rows tagged with the stream."""
+    S = tr.S
+    status = tr.status()
+    names = ["nkeypoints", "nmatches", "ninliers", "nmatches_map", "ok", "nlines", "line_matches",
+             "line_nmatches_map"]
+    cols = [st[k] for k in names[:4]] + [status[k] for k in names[4:]]
+    if with_local:
+        lst = tr.local_stats()
+        cols += [lst[k] for k in ("local_matches", "local_inliers", "local_line_matches",
+                                  "local_line_inliers")]
+    out = {"Tcw": np.ascontiguousarray(st["Tcw"], np.float32).reshape(S, 16),
+           "counts": np.stack(cols, 1).astype(np.float64)}
+    samp = np.sort(np.random.default_rng(0).choice(S, min(S, DUMP_STREAMS), replace=False))
+    out["sampled_streams"] = samp.astype(np.float64)
+    kps, desc, match, kls = [], [], [], []
+    for s in samp:
+        ku, d, m, o = tr.frame(int(s))
+        tag = np.full(len(ku), s, np.float64)
+        kps.append(np.stack([tag] + [ku[f].astype(np.float64) for f in ku.dtype.names], 1))
+        desc.append(d.astype(np.float32))
+        match.append(np.stack([tag, m.astype(np.float64), o.astype(np.float64)], 1))
+        if tr.use_lines:
+            kl, ld, lm, lo = tr.lines(int(s))
+            tag = np.full(len(kl), s, np.float64)
+            kls.append(np.concatenate(
+                [np.stack([tag] + [kl[f].astype(np.float64) for f in kl.dtype.names] +
+                          [lm.astype(np.float64), lo.astype(np.float64)], 1),
+                 ld.astype(np.float64)], 1))
+    out.update(keypoints=np.concatenate(kps), descriptors=np.concatenate(desc),
+               matches=np.concatenate(match))
+    if kls:
+        out["keylines"] = np.concatenate(kls)
+    return out
+
+
+def write_outputs(directory, arrays, rank=0):
+    """DIR/<name>.npy per array (rank r > 0: <name>_rank<r>.npy), float32 /
+    float64, DUMP_MAX_BYTES at most in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}")
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(d / (f"{name}.npy" if rank == 0 else f"{name}_rank{rank}.npy"), a)
+
+
 def map_capacity(total_steps):
     """Keyframe slots per stream for a tracker that runs `total_steps` steps:
     at most one keyframe per step, so the map never declines one (the
@@ -684,7 +789,10 @@ def run_workload(pkg, synth, args, workload, S, steps, warmup, rank, world, devi
     t1 = time.perf_counter()
     elapsed = max_over_ranks(dist, t1 - t0)
     st = tr.state()
-    tim = tr.timings(steps)                            # (steps, 11) ms, in-stream hipEvents
+    outputs = None
+    if args.dump_outputs and workload == args.workload:
+        outputs = tracker_outputs(tr, st, bool(args.local_map) or use_map)
+    tim = tr.timings(steps)                          # (steps, 11) ms, in-stream hipEvents
     avg = tim.mean(0)
     stages = dict(zip(tr.STAGES, [round(float(x), 4) for x in avg]))
     stage_avg = dict(zip(tr.STAGES, [float(x) for x in avg]))
@@ -741,7 +849,7 @@ def run_workload(pkg, synth, args, workload, S, steps, warmup, rank, world, devi
 
     # roofline of the dominant single-stage kernel
     n_kp = float(st["nkeypoints"].mean())
-    lsdc = lsd_counts(gray) if lines else None
+    lsdc = lsd_counts(gray) if lines and args.full else None   # oracle runs of its own
     ab = algorithmic_bytes(n_kp, fw, fh, wl["orb"])
     # candidates: every kernel's GPU time per step, a kernel launched in
     # several stages (k_pose: motion model, reference keyframe, local map)
@@ -898,7 +1006,7 @@ def run_workload(pkg, synth, args, workload, S, steps, warmup, rank, world, devi
     return dict(S=S, value=value, layout=L, elapsed=elapsed, stages=stages, tracking=tracking,
                 roof=roof, gray=gray, depth=depth, workload=wl["desc"], data=wl["data"],
                 image=f"{fw}x{fh}", nfeatures=wl["orb"][0], samp=samp, hist=hist, wname=workload,
-                pipelined=bool(pipelined), map=use_map, trk_load=trk_load)
+                pipelined=bool(pipelined), map=use_map, trk_load=trk_load, outputs=outputs)
 
 
 def run_ingress(pkg, synth, args, S, steps, warmup, rank, world, device, dist, voc=None,
@@ -1270,6 +1378,26 @@ def faithful_run(npz, pin=True):
     return out
 
 
+def write_detail(args, out):
+    """The full report's side file; returns the name the compact line carries
+    (relative to the repository when inside it), or None when there is none:
+    a plain run without --detail writes nothing, and a file that cannot be
+    written (a read-only tree) costs the report, never the result line."""
+    import tempfile
+    if args.detail is None and not args.full:
+        return None
+    detail = Path(args.detail) if args.detail else Path(tempfile.gettempdir()) / "bench_detail.json"
+    if not detail.is_absolute():
+        detail = ROOT / detail
+    try:
+        detail.parent.mkdir(parents=True, exist_ok=True)
+        detail.write_text(json.dumps(out) + "\n")
+    except OSError as e:
+        print(f"bench: detail file {detail} not written: {e}", file=sys.stderr, flush=True)
+        return None
+    return str(detail.relative_to(ROOT)) if detail.is_relative_to(ROOT) else str(detail)
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -1361,10 +1489,31 @@ def main():
                          "host-to-device inside the timed region; points runs only; 0 = skip)")
     ap.add_argument("--no-parity", action="store_true",
                     help="skip the oracle replay of the timed trackers' sampled streams")
-    ap.add_argument("--detail", default="gpurun_out/bench_detail.json",
+    ap.add_argument("--detail", default=None,
                     help="side file for the full report (stage times, sweeps, LSD floors, "
-                         "per-kernel GB/s); stdout's last line is the compact record")
+                         "per-kernel GB/s); stdout's last line is the compact record. Default: "
+                         "none for a plain run (nothing is written beside --dump-outputs), "
+                         "bench_detail.json in the system's temporary directory with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the other workloads' "
+                         "legs (secondary, stereo, rig, ingress), the oracle parity replay, the "
+                         "CPU baselines, the batch sweeps, the isolated steps, the "
+                         "TrackReferenceKeyFrame load steps and the LSD floors. Without it only "
+                         "the headline workload is set up, warmed up and timed, and the options "
+                         "of those legs have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed tracker computed in its "
+                         "last step (tracker_outputs) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--prepare", action="store_true",
+                    help="render the loops a plain run of these arguments reads into "
+                         ".bench_cache/ and exit (no GPU; __graft_entry__.build() runs it)")
     args = ap.parse_args()
+    if args.prepare:
+        return prepare(args)
+    if not args.full:
+        args.secondary_steps = args.stereo_steps = args.rig_steps = args.ingress_steps = 0
+        args.isolated_steps = args.sweep = args.trk_load = 0
+        args.no_cpu_baseline = args.no_parity = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU, started before anything here touches the GPU
@@ -1392,6 +1541,8 @@ def main():
     res = run_workload(pkg, synth, args, args.workload, args.streams, args.steps, args.warmup,
                        rank, world, device, dist, voc)
     res["nsteps"] = args.steps
+    if res["outputs"] is not None:
+        write_outputs(args.dump_outputs, res["outputs"], rank)
     # other BASELINE configs, same clock discipline, fewer steps (points runs only)
     others = {}
     if args.workload == "points" and args.secondary_steps > 0:
@@ -1520,14 +1671,7 @@ def main():
                     out[key]["dropin_frame"] = dropin_frame_latency(o["gray"], o["depth"],
                                                                     o["layout"], o["wname"])
         out["summary"] = leg_summary(out)
-        detail = Path(args.detail)
-        if not detail.is_absolute():
-            detail = ROOT / detail
-        detail.parent.mkdir(parents=True, exist_ok=True)
-        detail.write_text(json.dumps(out) + "\n")
-        line = json.dumps(compact_line(out, str(detail.relative_to(ROOT))
-                                       if detail.is_relative_to(ROOT) else str(detail)))
-        print(line, flush=True)
+        print(json.dumps(compact_line(out, write_detail(args, out))), flush=True)
     if dist:
         dist.destroy_process_group()
 

@@ -15,9 +15,9 @@ ROOT = Path(__file__).resolve().parents[1]
 
 def test_bench_two_ranks(tmp_path):
     detail = tmp_path / "detail.json"
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--streams", "16", "--steps", "2",
-           "--warmup", "1", "--loop", "8", "--secondary-steps", "0", "--stereo-steps", "0",
-           "--rig-steps", "0", "--no-cpu-baseline", "--sweep", "0", "--isolated-steps", "0",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--streams", "16",
+           "--steps", "2", "--warmup", "1", "--loop", "8", "--secondary-steps", "0",
+           "--stereo-steps", "0", "--rig-steps", "0", "--no-cpu-baseline", "--sweep", "0", "--isolated-steps", "0",
            "--detail", str(detail)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-3000:]
@@ -39,9 +39,9 @@ def test_bench_lines_1024_streams_parity(tmp_path):
     stream resident at once): the timed tracker's sampled streams 0, 512 and
     1023 match the oracle loop bit-exact (counts) / within POSE_TOL (pose)."""
     detail = tmp_path / "detail.json"
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", "lines", "--streams", "1024",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sweep", "0",
-           "--isolated-steps", "0", "--ingress-steps", "0", "--detail", str(detail)]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--workload", "lines",
+           "--streams", "1024", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+           "--sweep", "0", "--isolated-steps", "0", "--ingress-steps", "0", "--detail", str(detail)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-3000:]
     c = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])

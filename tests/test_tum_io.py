@@ -1,6 +1,6 @@
 """CPU tests of the host-side I/O and trajectory evaluator (orbpl.tum):
 settings, associations, SaveTrajectoryTUM format, quaternions, ATE."""
-import os
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -10,7 +10,16 @@ from _pkg import load_pkg
 load_pkg()
 import orbpl.tum as tum  # noqa: E402
 
-REF = "/root/reference"
+# the reference's recorded fr1_room run: its results/CameraTrajectory.txt and its
+# Examples/RGB-D/associate_with_groundtruth.txt, stored as data (gzip of each)
+FR1_ROOM = Path(__file__).resolve().parent / "golden" / "fr1_room"
+
+
+def _unpacked(name, tmp_path):
+    import gzip
+    p = tmp_path / name
+    p.write_bytes(gzip.decompress((FR1_ROOM / (name + ".gz")).read_bytes()))
+    return p
 
 
 def _rot(axis, ang):
@@ -95,12 +104,11 @@ def test_ate_alignment():
     assert np.allclose(tum.camera_centres(Tcw), [[0, 0, 0], [-1, 0, 0]])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
-def test_ate_of_the_reference_result():
+def test_ate_of_the_reference_result(tmp_path):
     """the reference's own fr1_room trajectory against the
-    ground-truth columns of its association file (read in place)."""
-    t, Twc = tum.load_trajectory_tum(f"{REF}/results/CameraTrajectory.txt")
-    a = tum.load_associations(f"{REF}/Examples/RGB-D/associate_with_groundtruth.txt")
+    ground-truth columns of its association file (copies under golden/)."""
+    t, Twc = tum.load_trajectory_tum(_unpacked("CameraTrajectory.txt", tmp_path))
+    a = tum.load_associations(_unpacked("associate_with_groundtruth.txt", tmp_path))
     assert np.array_equal(t, a["t_rgb"])
     r = tum.ate(Twc[:, :3, 3], tum.poses_from_rows(a["gt"])[:, :3, 3])
     assert r["n"] == 1352

@@ -5,7 +5,7 @@
 # pyramid + FAST span + octree + orientation/descriptor milliseconds.
 set -o pipefail
 mkdir -p gpurun_out/ab
-B="--no-cpu-baseline --no-parity --sweep 0 --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --isolated-steps 3"
+B="--full --no-cpu-baseline --no-parity --sweep 0 --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --isolated-steps 3"
 for r in $(seq 1 ${3:-2}); do
   for it in ${1:-cur}; do
     v=${it%%:*}; e=""; [ "$it" != "$v" ] && e=${it#*:}

@@ -5,7 +5,7 @@
 # and the batch-1 latency of the leg's sweep when present.
 set -o pipefail
 mkdir -p gpurun_out/abw
-C="--no-cpu-baseline --no-parity --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --isolated-steps 0"
+C="--full --no-cpu-baseline --no-parity --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --isolated-steps 0"
 for r in $(seq 1 ${3:-1}); do
   for w in ${2:-points lines}; do
     for it in ${1:-cur}; do

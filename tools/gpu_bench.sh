@@ -3,9 +3,10 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
+O=$_   # the directory made above
 cd $R
 start=$(date +%s)
-timeout -k 10 1100 python -u bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err || { echo "bench failed"; tail -20 gpurun_out/bench_default.err; exit 1; }
+timeout -k 10 1100 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -20 $O/bench_default.err; exit 1; }
 echo "bench ok in $(( $(date +%s) - start )) s"
 python3 - <<'PY'
 import json

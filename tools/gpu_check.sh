@@ -9,6 +9,7 @@ mkdir -p gpurun_out
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > gpurun_out/gpu_tests.log 2>&1
 rc=$?; echo "pytest exit $rc"; tail -3 gpurun_out/gpu_tests.log
 [ $rc -ne 0 ] && exit $rc
+set -- --full "$@"   # the whole bench: every leg, parity, CPU baselines, sweeps
 timeout -k 10 420 python bench.py "$@" > gpurun_out/bench.log 2>&1
 rc=$?; echo "bench exit $rc"; tail -c 600 gpurun_out/bench.log
 exit $rc

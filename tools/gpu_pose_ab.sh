@@ -22,7 +22,7 @@ for v in $VARIANTS; do
   ) || { echo "probe $name failed"; tail -5 $O/probe_$name.log; exit 1; }
   echo "== $name"; cat $O/probe_$name.log
 done
-timeout -k 10 600 python -u bench.py --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --sweep 0 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --sweep 0 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 python3 - <<PY
 import json
 d = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])
@@ -31,7 +31,7 @@ print("stages", d["stage_ms"])
 print("isolated", d["roofline"].get("isolated", {}).get("stage_ms"))
 PY
 if [ -n "$BENCH2_ENV" ]; then
-  env $BENCH2_ENV timeout -k 10 600 python -u bench.py --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --sweep 0 --no-cpu-baseline > $O/bench2.json 2> $O/bench2.err || { echo "bench2 failed"; tail -20 $O/bench2.err; exit 1; }
+  env $BENCH2_ENV timeout -k 10 600 python -u bench.py --full --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --sweep 0 --no-cpu-baseline > $O/bench2.json 2> $O/bench2.err || { echo "bench2 failed"; tail -20 $O/bench2.err; exit 1; }
   python3 - <<PY
 import json
 d = json.loads(open("$O/bench2.json").read().strip().splitlines()[-1])

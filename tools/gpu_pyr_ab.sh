@@ -10,7 +10,7 @@ mkdir -p $O
 cd $R
 timeout -k 10 300 python -u -m pytest tests/test_gpu_orb.py -x -q --timeout 200 --timeout-method thread > $O/orb_tests.log 2>&1
 rc=$?; echo "orb tests exit $rc: $(tail -1 $O/orb_tests.log)"; [ $rc -ne 0 ] && exit $rc
-B="--no-cpu-baseline --no-parity --sweep 0 --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --steps 20 --warmup 5"
+B="--full --no-cpu-baseline --no-parity --sweep 0 --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --steps 20 --warmup 5"
 for r in 1 2; do
   for lib in cur $V; do
     L=""; [ $lib != cur ] && L=variants/$lib/liborbpl.so

@@ -8,6 +8,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_map.py -q --timeout 300 --t
 rc=$?
 echo "map tests rc=$rc"; tail -2 gpurun_out/gpu_map_q.log
 if [ $rc -ne 0 ]; then grep -E "assert|Error" gpurun_out/gpu_map_q.log | head -20; exit 1; fi
+QUICK_ARGS="--full $QUICK_ARGS"   # parity and the isolated steps are read below
 timeout -k 10 600 python -u bench.py --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0 --sweep 0 --no-cpu-baseline $QUICK_ARGS > gpurun_out/bench_q.json 2> gpurun_out/bench_q.err || { echo "bench failed"; tail -20 gpurun_out/bench_q.err; exit 1; }
 python3 - <<'PY'
 import json

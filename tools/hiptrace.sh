@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/hiptrace_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --hip-trace --kernel-trace -d $out -o run --output-format csv -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-parity --sweep 0 --ingress-steps 0 --isolated-steps 0 "$@" > $out/trace.log 2>&1 || { echo "trace failed"; tail -5 $out/trace.log; exit 1; }
+timeout -k 10 300 rocprofv3 --hip-trace --kernel-trace -d $out -o run --output-format csv -- python3 $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-parity --sweep 0 --ingress-steps 0 --isolated-steps 0 "$@" > $out/trace.log 2>&1 || { echo "trace failed"; tail -5 $out/trace.log; exit 1; }
 python3 - "$out" <<'PY'
 import csv, glob, sys
 out = sys.argv[1]

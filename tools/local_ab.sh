@@ -6,7 +6,7 @@ set -o pipefail
 mkdir -p gpurun_out
 timeout -k 10 300 python -u -m pytest tests -m gpu -x -q -k "${1:-local}" --timeout 200 --timeout-method thread > gpurun_out/lt.log 2>&1
 rc=$?; tail -3 gpurun_out/lt.log; [ $rc -ne 0 ] && exit $rc
-B="--no-cpu-baseline --no-parity --sweep 0 --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0"
+B="--full --no-cpu-baseline --no-parity --sweep 0 --secondary-steps 0 --stereo-steps 0 --rig-steps 0 --ingress-steps 0"
 ORBPL_LIB=variants/lprof/liborbpl.so timeout -k 10 300 python bench.py --streams 1024 --steps 3 --warmup 2 --isolated-steps 0 $B > gpurun_out/lprof.log 2>&1 || exit 1
 grep "local blk" gpurun_out/lprof.log | tail -8
 timeout -k 10 200 python bench.py --streams 1024 --steps 10 --warmup 3 --isolated-steps 3 $B > gpurun_out/b1024.log 2>&1 || exit 1
