@@ -71,6 +71,8 @@ __host__ __device__ constexpr int fast_wave_words(int win_w, int win_h) {
 
 typedef short fshort2 __attribute__((ext_vector_type(2)));
 typedef unsigned short fushort2 __attribute__((ext_vector_type(2)));
+typedef uint32_t fuint3 __attribute__((ext_vector_type(3)));
+typedef fuint3 fuint3_a4 __attribute__((aligned(4)));   // three dwords at a dword address
 
 // Integer and address helpers for the per-lane index arithmetic.
 // a * b for operands that fit 16 bits: the zero / sign extensions let the
@@ -927,16 +929,10 @@ __device__ __forceinline__ void nms_pair(const uint32_t* M, int ps, int r, int q
 __device__ __forceinline__ int wave_incl_scan(int v);
 
 // minimum waves per SIMD for k_fast_cells (register budget); see DESIGN.md
-// (6: the MM3 score fit 80 VGPRs without spills; since the DPP neighbours and
-// the scalar wave index it takes 71 = 7 waves; 8 fits 63 without spills but
-// gains nothing on the headline, profiles/r06/ab/occupancy_fast_pyr_ab.txt)
+// (6: the MM3 score fit 80 VGPRs without spills; with the NMS out of the walk
+// it takes 62 = 8 waves)
 #ifndef ORBPL_FAST_MINW
 #define ORBPL_FAST_MINW 6
-#endif
-// neighbour pixels of the walk's row from the adjacent lanes by DPP wave
-// shifts (1 VALU each) instead of ds_bpermute with per-row lane arithmetic
-#ifndef ORBPL_FAST_DPP
-#define ORBPL_FAST_DPP 1
 #endif
 // the ring's next row loaded one row ahead of its use
 #ifndef ORBPL_FAST_PREFETCH
@@ -966,42 +962,49 @@ __global__ void __launch_bounds__(256, ORBPL_FAST_MINW) k_fast_cells(const uint8
   const int pw = fast_pstride(g->fast_win_w);   // u16 per m-plane row
   const int pw2 = pw >> 1;                      // dwords per row: dword d = pixels (2d, 2d+1)
   uint32_t* M = fast_smem + wave * fast_wave_words(g->fast_win_w, g->fast_win_h);
-  // candidate bit masks of detection row r (bit p = column pair p):
-  // mask[4 r + j], j = 0 lo / 1 hi pixel at min_th, 2 lo / 3 hi at ini_th
+  // bit masks of detection row r (bit p = column pair p), each word written
+  // whole by one lane: mask[4 r + j], j = 0 lo / 1 hi pixel: during the walk
+  // the pixels with m >= ini_th + 1, in a fallback cell the candidates at
+  // min_th; j = 2 lo / 3 hi: the candidates at ini_th
   uint32_t* mask = M + g->fast_win_h * pw2;
   const LevelGeom& L = g->lv[cg.level];
   const int cols = cg.x1 - cg.x0, rows = cg.y1 - cg.y0;
-  // zero the window's m (outside the detection region = 0) and the masks
+  // zero the window's m (outside the detection region = 0)
   {
     const int nq = rows * pw2 / 4;
     for (int k = lane; k < nq; k += 64) reinterpret_cast<uint4*>(M)[k] = make_uint4(0, 0, 0, 0);
-    for (int k = lane; k < 4 * g->fast_win_h; k += 64) mask[k] = 0;
   }
   __builtin_amdgcn_wave_barrier();
   const int t_ini = max((ini_th < 0 ? 0 : (ini_th > 255 ? 255 : ini_th)) + 1, 2);
   const int t_min = max((min_th < 0 ? 0 : (min_th > 255 ? 255 : min_th)) + 1, 2);
   // ---- m for the detection region rows [3, rows-3), cols [3, cols-3):
   // lane = (column pair p, row segment); each lane walks its rows with the
-  // 7 ring rows of its pair in registers, loaded straight from the level.
-  // The raw-m NMS (a candidate is a local maximum of m with m >= T; the
-  // neighbours' raw m stand in for cv::FAST's thresholded scores, which only
-  // differ where m < T <= the centre's) runs in the same walk one row behind:
-  // the row above / below come from the lane's own registers, the left / right
-  // neighbour pixels from the adjacent lanes. The first and last row of each
-  // segment are finished from the m plane in LDS afterwards. ----
+  // 7 ring rows of its pair in registers, loaded straight from the level,
+  // and stores m into the plane. The walk only records which pixels reach
+  // ini_th (a ballot per row; the segment's first lane stores its bit field):
+  // the 3x3 NMS runs afterwards from the plane, for those pixels alone. ----
   const int dr = rows - 6, dc = cols - 6;
-  const int np = (dc + 1) >> 1;
+  const int np = (dc + 1) >> 1;   // <= 30: windows are at most 66 wide (orb_geom.cpp)
   const uint32_t inv_np = div_inv(np);
   const int npair = (dr > 0 && dc > 0) ? dr * np : 0;
   uint16_t* M16 = reinterpret_cast<uint16_t*>(M);
-  int nseg = 1, rps = dr;
-  bool any_ini = false;
+  // the lane's pair and row segment [ra, rb) (empty past the last segment)
+  const int nseg = npair > 0 ? max(1, 64 / np) : 1;
+  const int rps = (dr + nseg - 1) / nseg;
+  const int seg = div_small(lane, inv_np), p = lane - seg * np;
+  const bool in_seg = npair > 0 && seg < nseg;
+  const int ra = in_seg ? seg * rps : 0, rb = in_seg ? min(ra + rps, dr) : 0;
+  const int nit = __builtin_amdgcn_readfirstlane(rps);   // the longest segment
+  const uint32_t npmask = np > 0 ? (1u << np) - 1u : 0u;
+  // words 0 / 1 of a row's masks from the wave's ballots: the segment starts
+  // at this lane (p == 0), its np pairs are the next np ballot bits
+  auto store_row_bits = [&](int r, bool act, unsigned long long blo, unsigned long long bhi)
+      __attribute__((always_inline)) {
+    if (act && p == 0)
+      *reinterpret_cast<uint2*>(mask + 4 * r) =
+          make_uint2((uint32_t)(blo >> lane) & npmask, (uint32_t)(bhi >> lane) & npmask);
+  };
   if (npair > 0) {
-    nseg = max(1, 64 / np);
-    rps = (dr + nseg - 1) / nseg;
-    const int seg = div_small(lane, inv_np), p = lane - seg * np;
-    const bool in_seg = seg < nseg;
-    const int ra = in_seg ? seg * rps : 0, rb = in_seg ? min(ra + rps, dr) : 0;
     const int cx = cg.x0 + 3 + 2 * p;                    // content column of the left centre
     const int abase = (cx - 3) & ~3;
     const uint32_t o = (uint32_t)((cx - 3) - abase);
@@ -1011,24 +1014,18 @@ __global__ void __launch_bounds__(256, ORBPL_FAST_MINW) k_fast_cells(const uint8
     const uint8_t* wrow = pyr + (long long)f * g->pyr_bytes + content_off(L, 0, cg.y0);
     const uint32_t acol = (uint32_t)abase;
     const bool has_hi = 2 * p + 1 < dc;
-    const bool has_left = p > 0, has_right = p + 1 < np;
-    const uint32_t pbit = 1u << p;
+    const uint32_t t_ini_hi = (uint32_t)t_ini << 16;
     uint2 R[7];
     if (in_seg) {
 #pragma unroll
       for (int k = 0; k < 6; k++) R[k + 1] = load_ring_row(wrow, umul24((uint32_t)(ra + k), pitch) + acol, o);
     }
-    // rows r-1, r-2 of the walk: packed m, 3-wide row max, centre-excluded max
-    uint32_t m1 = 0, rmax1 = 0, rmax2 = 0, cmax1 = 0;
-    const int nit = __builtin_amdgcn_readfirstlane(rps);   // the longest segment
 #if ORBPL_FAST_PREFETCH
-    // the next ring row's dwords are loaded one row ahead
-    uint32_t nw0 = 0, nw1 = 0, nw2 = 0;
+    // the next ring row's dwords are loaded one row ahead, as one 3-dword
+    // value: the load then lands in the registers the next row reads
+    fuint3 nw = {0, 0, 0};
     auto ring_raw = [&](int row) __attribute__((always_inline)) {
-      const uint8_t* q = wrow + (umul24((uint32_t)row, pitch) + acol);
-      nw0 = *reinterpret_cast<const uint32_t*>(q);
-      nw1 = *reinterpret_cast<const uint32_t*>(q + 4);
-      nw2 = *reinterpret_cast<const uint32_t*>(q + 8);
+      nw = *reinterpret_cast<const fuint3_a4*>(wrow + (umul24((uint32_t)row, pitch) + acol));
     };
     if (in_seg && ra < rb) ring_raw(ra + 6);
 #endif
@@ -1040,8 +1037,8 @@ __global__ void __launch_bounds__(256, ORBPL_FAST_MINW) k_fast_cells(const uint8
 #pragma unroll
         for (int k = 0; k < 6; k++) R[k] = R[k + 1];
 #if ORBPL_FAST_PREFETCH
-        R[6] = make_uint2(__builtin_amdgcn_alignbyte(nw1, nw0, o), __builtin_amdgcn_alignbyte(nw2, nw1, o));
-        if (r + 1 < rb) ring_raw(r + 7);
+        R[6] = make_uint2(__builtin_amdgcn_alignbyte(nw.y, nw.x, o), __builtin_amdgcn_alignbyte(nw.z, nw.y, o));
+        ring_raw(min(r + 7, rb + 5));   // the segment's last row again where the walk ends
 #else
         R[6] = load_ring_row(wrow, umul24((uint32_t)(r + 6), pitch) + acol, o);
 #endif
@@ -1058,83 +1055,68 @@ __global__ void __launch_bounds__(256, ORBPL_FAST_MINW) k_fast_cells(const uint8
         M16[mo] = (uint16_t)lo;   // window column x = 3 + 2p
         M16[mo + 1] = (uint16_t)hi;
       }
-      // all lanes: neighbour pixels of the same row from the adjacent lanes
-#if ORBPL_FAST_DPP
-      // DPP wave shifts (lane i <- lane i - 1 / i + 1; lane 0 / 63 read 0)
-      const uint32_t lhi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(m >> 16), 0x138, 0xf, 0xf, false);
-      const uint32_t rlo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(m & 0xFFFFu), 0x130, 0xf, 0xf, false);
-#else
-      const uint32_t lhi = (uint32_t)__shfl_up((int)(m >> 16), 1, 64);
-      const uint32_t rlo = (uint32_t)__shfl_down((int)(m & 0xFFFFu), 1, 64);
-#endif
-      if (act) {
-        const uint32_t Pl = (has_left ? lhi : 0u) | (m << 16);        // (x-1, x)
-        const uint32_t Pr = (m >> 16) | ((has_right ? rlo : 0u) << 16);  // (x+1, x+2)
-        const fushort2 cm = pmaxu(as_u2(Pl), as_u2(Pr));
-        const uint32_t cmax = __builtin_bit_cast(uint32_t, cm);
-        const uint32_t rmax = __builtin_bit_cast(uint32_t, pmaxu(cm, as_u2(m)));
-        if (i >= 2) {
-          // NMS of row r-1 (interior: rows r-2 and r are this segment's)
-          const fushort2 mx = pmaxu(pmaxu(as_u2(rmax2), as_u2(rmax)), as_u2(cmax1));
-          const fushort2 mc = as_u2(m1);
-          const bool lmax_lo = mc.x > mx.x, lmax_hi = mc.y > mx.y;
-          const int row = r - 1;
-          uint32_t* mr = mask + 4 * row;
-          if (lmax_lo && mc.x >= t_min) atomicOr(mr, pbit);
-          if (lmax_hi && mc.y >= t_min) atomicOr(mr + 1, pbit);
-          const bool ilo = lmax_lo && mc.x >= t_ini, ihi = lmax_hi && mc.y >= t_ini;
-          if (ilo) atomicOr(mr + 2, pbit);
-          if (ihi) atomicOr(mr + 3, pbit);
-          any_ini |= ilo || ihi;
-        }
-        rmax2 = rmax1;
-        rmax1 = rmax;
-        cmax1 = cmax;
-        m1 = m;
-      }
+      // all lanes (m = 0 where idle): the row's pixels that reach ini_th
+      store_row_bits(r, act, __ballot((m & 0xFFFFu) >= (uint32_t)t_ini), __ballot(m >= t_ini_hi));
     }
   }
   __builtin_amdgcn_wave_barrier();
-  // ---- segment edge rows (first and last of each segment) from the m plane ----
+  // ---- 3x3 NMS at ini_th for the recorded pixels only: keep p <=> m > max
+  // of its 8 neighbours' raw m (zero outside the detection region). Lane =
+  // (detection row, lo / hi pixel of the pairs) walks the set bits of its
+  // record word and writes the row's candidate word whole. ----
+  bool any_ini = false;
   if (npair > 0) {
-    const int nedge = 2 * nseg * np;
-    for (int k = lane; k < nedge; k += 64) {
-      const int e = div_small(k, inv_np), p = k - e * np;
-      const int sg = e >> 1;
-      const int ra = sg * rps, rb = min(ra + rps, dr);
-      if (ra >= rb) continue;
-      const int row = (e & 1) ? rb - 1 : ra;
-      if ((e & 1) && rb - 1 == ra) continue;   // one-row segment: done once
-      // rows wr-1, wr, wr+1: dword 1+p = pixels (x-1, x), dword 2+p = (x+1, x+2)
-      fushort2 rm[3], cmc = {0, 0}, m = {0, 0};
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        const uint32_t* w = M + (row + 2 + d) * pw2 + 1 + p;
-        const uint32_t A = w[0], B = w[1];
-        const fushort2 cm = pmaxu(as_u2(A), as_u2(B));
-        const fushort2 mm = as_u2(__builtin_amdgcn_perm(B, A, 0x05040302u));   // (x, x+1)
-        rm[d] = pmaxu(cm, mm);
-        if (d == 1) {
-          cmc = cm;
-          m = mm;
-        }
+    for (int k = lane; k < 2 * dr; k += 64) {
+      const int row = k >> 1, half = k & 1;
+      uint32_t rem = mask[4 * row + half], keep = 0;
+      // u16 index of the pixel left of pair 0's centre on window row row + 2
+      const uint16_t* c0 = M16 + umul24((uint32_t)(row + 2), (uint32_t)pw) + 2 + half;
+      while (rem) {
+        const int q = __builtin_ctz(rem);
+        rem &= rem - 1;
+        const uint16_t* c = c0 + 2 * q;
+        const uint32_t up = max(max((uint32_t)c[0], (uint32_t)c[1]), (uint32_t)c[2]);
+        const uint32_t dn = max(max((uint32_t)c[2 * pw], (uint32_t)c[2 * pw + 1]), (uint32_t)c[2 * pw + 2]);
+        const uint32_t mx = max(max(up, dn), max((uint32_t)c[pw], (uint32_t)c[pw + 2]));
+        if ((uint32_t)c[pw + 1] > mx) keep |= 1u << q;
       }
-      const fushort2 mx = pmaxu(pmaxu(rm[0], rm[2]), cmc);
-      const bool lmax_lo = m.x > mx.x, lmax_hi = m.y > mx.y;
-      const uint32_t pbit = 1u << p;
-      uint32_t* mr = mask + 4 * row;
-      if (lmax_lo && m.x >= t_min) atomicOr(mr, pbit);
-      if (lmax_hi && m.y >= t_min) atomicOr(mr + 1, pbit);
-      const bool ilo = lmax_lo && m.x >= t_ini, ihi = lmax_hi && m.y >= t_ini;
-      if (ilo) atomicOr(mr + 2, pbit);
-      if (ihi) atomicOr(mr + 3, pbit);
-      any_ini |= ilo || ihi;
+      mask[4 * row + 2 + half] = keep;
+      any_ini |= keep != 0;
+    }
+  }
+  const bool use_ini = __ballot(any_ini) != 0ull;
+  // ---- no corner at ini_th: the dense NMS at min_th over all rows from the
+  // plane, in the walk's lane layout (wave-uniform branch) ----
+  if (!use_ini && npair > 0) {
+    for (int i = 0; i < nit; i++) {
+      const int r = ra + i;
+      const bool act = r < rb;
+      bool klo = false, khi = false;
+      if (act) {
+        // rows wr-1, wr, wr+1: dword 1+p = pixels (x-1, x), dword 2+p = (x+1, x+2)
+        fushort2 rm[3], cmc = {0, 0}, m = {0, 0};
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+          const uint32_t* w = M + (r + 2 + d) * pw2 + 1 + p;
+          const uint32_t A = w[0], B = w[1];
+          const fushort2 cm = pmaxu(as_u2(A), as_u2(B));
+          const fushort2 mm = as_u2(__builtin_amdgcn_perm(B, A, 0x05040302u));   // (x, x+1)
+          rm[d] = pmaxu(cm, mm);
+          if (d == 1) {
+            cmc = cm;
+            m = mm;
+          }
+        }
+        const fushort2 mx = pmaxu(pmaxu(rm[0], rm[2]), cmc);
+        klo = m.x > mx.x && m.x >= t_min;
+        khi = m.y > mx.y && m.y >= t_min;
+      }
+      store_row_bits(r, act, __ballot(klo), __ballot(khi));
     }
   }
   __builtin_amdgcn_wave_barrier();
   // ---- emission in raster order: cv::FAST at ini_th, or at min_th when the
   // cell has no corner at ini_th (ORBextractor.cc:807-817); lane = row ----
-  const bool use_ini = __ballot(any_ini) != 0ull;
   const int j0 = use_ini ? 2 : 0;
   uint32_t* out = cell_cands + ((long long)f * g->ncells_total + cell) * slots;
   const int xoff = cg.x0 - kMinBorder, yoff = cg.y0 - kMinBorder;
@@ -1248,9 +1230,13 @@ __device__ int block_excl_scan(int* vals, int n, int* s_wsum) {
 // 8 KB keeps two blocks per CU.
 constexpr int kOctLdsCand = 4096;
 // first pyramid level whose octree launch runs one-wave workgroups (the
-// launch of a level group starting there; ORBPL_OCT_WAVE_FROM overrides)
+// launch of a level group starting there; the environment variable
+// ORBPL_OCT_WAVE_FROM, read when an extractor is created, overrides).
+// Default: none, every level as a 256-thread workgroup (the one-wave path
+// measured about 1.2 % slower on the headline,
+// profiles/r06/ab/octree_ab.txt)
 #ifndef ORBPL_OCT_WAVE_FROM
-#define ORBPL_OCT_WAVE_FROM 3
+#define ORBPL_OCT_WAVE_FROM kMaxLevels
 #endif
 constexpr int kOctWaveFrom = ORBPL_OCT_WAVE_FROM;
 
@@ -1978,7 +1964,8 @@ void launch_fast(const OrbGeom& hg, const OrbGeom* dg, const CellGeom* cells, co
 
 void launch_octree(const OrbGeom& hg, const OrbGeom* dg, const uint32_t* cell_cands,
                    const int* cell_counts, uint32_t* kcand, int* knode, uint32_t* kp_list,
-                   int* kp_count, int* err_flag, int batch, int l0, int l1, hipStream_t s) {
+                   int* kp_count, int* err_flag, int batch, int l0, int l1, int wave_from,
+                   hipStream_t s) {
   set_smem_attr((const void*)k_octree<1024, 256>, sizeof(OctShared<1024>));
   int cap = 0;
   for (int l = 0; l < hg.nlevels; l++) cap = std::max(cap, hg.lv[l].kp_cap);
@@ -1987,11 +1974,8 @@ void launch_octree(const OrbGeom& hg, const OrbGeom* dg, const uint32_t* cell_ca
     (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_oct_prof_on), &on, sizeof(int), 0,
                                  hipMemcpyHostToDevice, s);
   }
-  // levels from ORBPL_OCT_WAVE_FROM on (default 3: the coarse levels, a few
-  // hundred candidates each) as one-wave workgroups; 0 = all, nlevels = none
-  const char* wf = getenv("ORBPL_OCT_WAVE_FROM");   // read per launch: tests vary it
-  const int wave_from = wf ? atoi(wf) : kOctWaveFrom;
-  const bool one_wave = l0 >= wave_from;
+  // levels from wave_from on as one-wave workgroups; 0 = all, nlevels = none
+  const bool one_wave = l0 >= (wave_from >= 0 ? wave_from : kOctWaveFrom);
 #define ORBPL_OCT_LAUNCH(CAP)                                                                   \
   if (one_wave)                                                                                 \
     hipLaunchKernelGGL((k_octree<CAP, 64>), dim3(l1 - l0, batch), dim3(64),                    \

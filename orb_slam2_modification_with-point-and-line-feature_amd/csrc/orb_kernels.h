@@ -31,9 +31,12 @@ void launch_pyramid(const OrbGeom& hg, const OrbGeom* dg, const uint8_t* img, in
 void launch_fast(const OrbGeom& hg, const OrbGeom* dg, const CellGeom* cells, const uint8_t* pyr,
                  uint32_t* cell_cands, int* cell_counts, int ini_th, int min_th, int batch,
                  int l0, int l1, hipStream_t s);
+// wave_from: first level whose launch runs one-wave workgroups (< 0: the
+// built-in default, none)
 void launch_octree(const OrbGeom& hg, const OrbGeom* dg, const uint32_t* cell_cands,
                    const int* cell_counts, uint32_t* kcand, int* knode, uint32_t* kp_list,
-                   int* kp_count, int* err_flag, int batch, int l0, int l1, hipStream_t s);
+                   int* kp_count, int* err_flag, int batch, int l0, int l1, int wave_from,
+                   hipStream_t s);
 void launch_orient_desc(const OrbGeom& hg, const OrbGeom* dg, const uint8_t* pyr,
                         const uint8_t* blur, const uint32_t* kp_list, const int* kp_count,
                         orbpl_keypoint_dev* out_kps, uint8_t* out_desc, int kp_pitch, int* out_n,

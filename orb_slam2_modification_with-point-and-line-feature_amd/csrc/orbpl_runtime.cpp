@@ -163,6 +163,7 @@ struct orbx_ctx {
   long long* d_pyr_prof = nullptr;   // ORBPL_PYR_PROFILE: k_pyramid phase stamps
   int pyr_bands = 0;           // 0 = choose per batch (ORBPL_PYR_BANDS overrides)
   int group_bands[kFastGroups] = {0, 0, 0, 0};   // per level group (0 = nb above)
+  int oct_wave_from = -1;   // ORBPL_OCT_WAVE_FROM at creation (< 0: launch_octree's default)
   uint8_t* d_in = nullptr;
   uint8_t* d_pyr = nullptr;
   uint8_t* d_blur = nullptr;
@@ -428,6 +429,9 @@ int orbx_create(const orbpl_orb_params* p, int width, int height, int max_batch,
       c->group_bands[gi++] = (b == 1 || b == 2 || b == 4 || b == 8) ? b : 0;
     }
   }
+  // ORBPL_OCT_WAVE_FROM=l: the octree launches of level groups starting at
+  // level l or above run one-wave workgroups (0 = all; A/B and tests)
+  if (const char* e = getenv("ORBPL_OCT_WAVE_FROM")) c->oct_wave_from = std::max(0, atoi(e));
   if (getenv("ORBPL_PYR_PROFILE")) {
     CK(hipMalloc(&c->d_pyr_prof, 8 * (1 + 4 * kMaxLevels)));
     CK(hipMemsetAsync(c->d_pyr_prof, 0, 8 * (1 + 4 * kMaxLevels), c->stream));
@@ -580,7 +584,8 @@ int orbx_run(orbx_ctx* c, const uint8_t* d_imgs, int batch, int stride, long lon
     if (!pipe) HIP_CHECK(hipEventRecord(ev[3], s));
     HIP_CHECK(bracket(1, gi, 0, fs));
     launch_octree(g, c->d_geom, c->d_cell_cands, c->d_cell_counts, c->d_kcand, c->d_knode,
-                  c->d_kp_list, c->d_kp_count, c->d_err, batch, l0, l1, fs);
+                  c->d_kp_list, c->d_kp_count, c->d_err, batch, l0, l1, c->oct_wave_from,
+                  fs);
     HIP_CHECK(bracket(1, gi, 1, fs));
     if (!pipe) HIP_CHECK(hipEventRecord(ev[4], s));
     l0 = l1;
