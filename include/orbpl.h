@@ -347,6 +347,124 @@ int orbm_search_by_bow(int nkf, const int32_t* kf_node, const uint8_t* kf_valid,
                        int32_t* match, int* nmatches);
 
 /* ------------------------------------------------------------------------
+ * Tracking::Relocalization (Tracking.cc:2049-2269): its place recognition and
+ * its projection matcher. With orbv_transform (Frame::ComputeBoW),
+ * orbm_search_by_bow and orbpl_pose_optimization the function lacks only
+ * PnPsolver.
+ * ---------------------------------------------------------------------- */
+#define ORBKF_MAX_KEYFRAMES 64   /* keyframes per database (ORBPL_MAP_KF's maximum) */
+#define ORBKF_MAX_WORDS 4096     /* BowVector entries per vector (orbv_transform's cap) */
+#define ORBKF_COVISIBLES 10      /* GetBestCovisibilityKeyFrames(10) */
+/* KeyFrameDatabase::DetectRelocalizationCandidates(Frame*)
+ * (KeyFrameDatabase.cc:274-412) for one (database, query) pair. The database
+ * is its nkf keyframes in add() order (erased or bad keyframes are absent):
+ * their BowVectors as CSR (kf_off[nkf + 1], kf_off[0] = 0; words ascending
+ * within a keyframe), covis[nkf][10] = GetBestCovisibilityKeyFrames(10) as
+ * database indices in that order (-1: padding, or a neighbour that is not in
+ * the database), reloc_score[nkf] = mRelocScore: in/out, per-keyframe state
+ * that persists across queries and starts at 0.0f (the reference never
+ * initialises it) - a keyframe scored in this query is
+ * overwritten, every other entry is kept. The query is F->mBowVec (words
+ * ascending). Outputs: cand[64] / *ncand = the returned vector as database
+ * indices in the reference's order; common_words[nkf] (may be NULL) =
+ * mnRelocWords, 0 for a keyframe that shares no word. */
+typedef struct orbkf_problem {
+  int32_t nkf;
+  const int32_t* kf_off;
+  const uint32_t* kf_words;
+  const double* kf_vals;
+  const int32_t* covis;
+  float* reloc_score;
+  int32_t nq_words;
+  const uint32_t* q_words;
+  const double* q_vals;
+  int32_t* cand;
+  int32_t* ncand;
+  int32_t* common_words;
+} orbkf_problem;
+/* nq independent problems in one launch (one lost frame per stream, each with
+ * its own map). scoring = the vocabulary's ScoringType (orbv_info): only
+ * L1_NORM = 0 (ORBvoc's) is built, anything else returns ORBPL_ERR_ARG, as do
+ * more than 64 keyframes or more than 4096 entries in a vector. */
+int orbkf_detect_reloc(const orbkf_problem* problems, int nq, int scoring);
+/* The same over pitched device arrays, asynchronous on `stream` (a
+ * hipStream_t, NULL = the null stream). Per-keyframe arrays hold 64 entries
+ * per problem (d_kf_off 65, d_covis 64 x 10); problem p's keyframe entries
+ * start at p * ent_pitch, its query at p * q_pitch. Counts above the caps
+ * are clamped. d_common_words may be NULL. */
+typedef struct orbkf_device_batch {
+  const int32_t* d_nkf;
+  const int32_t* d_kf_off;
+  const uint32_t* d_kf_words;
+  const double* d_kf_vals;
+  int64_t ent_pitch;
+  const int32_t* d_covis;
+  float* d_reloc_score;
+  const int32_t* d_q_n;
+  const uint32_t* d_q_words;
+  const double* d_q_vals;
+  int64_t q_pitch;
+  int32_t* d_cand;
+  int32_t* d_ncand;
+  int32_t* d_common_words;
+} orbkf_device_batch;
+int orbkf_detect_reloc_batch_device(const orbkf_device_batch* b, int nq, int scoring,
+                                    void* stream);
+
+/* ORBmatcher(nnratio, checkOri).SearchByProjection(Frame& CurrentFrame,
+ * KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th, ORBdist)
+ * (ORBmatcher.cc:1891-2024; Tracking.cc:2201, 2215). cur->Tcw = the pose the
+ * PnP solver / the optimiser gave (cur->uright is not read). cur_has_mp[i] =
+ * CurrentFrame.mvpMapPoints[i] != NULL on entry. Per keyframe feature j <
+ * nkf: kf_angle = mvKeysUn[j].angle, kf_valid = its map point exists and is
+ * not bad, kf_found = it is in sAlreadyFound, the point's world position,
+ * raw mfMinDistance / mfMaxDistance (the 0.8f / 1.2f applied inside, as in
+ * orbpl_frame_is_in_frustum) and descriptor. Keyframe features in index
+ * order; a keypoint that holds a map point - on entry or claimed earlier in
+ * the call - is skipped; the first minimum wins and is accepted on bestDist
+ * <= orb_dist; searched levels [level - 1, level + 1], radius th *
+ * scale[level]; then the 30-bin rotation check. mfLogScaleFactor is taken
+ * from scale_factors[1]. match[i] = keyframe feature assigned to keypoint i
+ * in this call, or -1; *nmatches = the return value. n, nkf <= 2048. The
+ * reference has no invzc < 0 test here; a projection that is not a number is
+ * rejected. */
+int orbm_search_by_projection_kf(const orbpl_camera* cam, const float* scale_factors, int nlevels,
+                                 const orbpl_match_current* cur, const uint8_t* cur_has_mp,
+                                 int nkf, const float* kf_angle, const uint8_t* kf_valid,
+                                 const uint8_t* kf_found, const float* mp_xyz,
+                                 const float* mp_min_dist, const float* mp_max_dist,
+                                 const uint8_t* mp_desc, float th, int orb_dist, int check_ori,
+                                 int32_t* match, int* nmatches);
+/* The same for `batch` problems over pitched device arrays, asynchronous on
+ * `stream`: problem b's current-frame arrays start at b * kp_pitch entries
+ * (d_cur_n[b] of them), its keyframe arrays at b * kf_pitch (d_kf_n[b]), its
+ * pose at d_Tcw + 16 b; d_match is per current keypoint, d_nmatches[batch].
+ * Pitches <= 2048; counts above a pitch are clamped. */
+typedef struct orbm_kf_device_batch {
+  int32_t kp_pitch;
+  const int32_t* d_cur_n;
+  const float* d_Tcw;
+  const orbpl_keypoint* d_cur_kps_un;
+  const uint8_t* d_cur_desc;
+  const uint8_t* d_cur_has_mp;
+  int32_t kf_pitch;
+  const int32_t* d_kf_n;
+  const float* d_kf_angle;
+  const uint8_t* d_kf_valid;
+  const uint8_t* d_kf_found;
+  const float* d_mp_xyz;
+  const float* d_mp_min_dist;
+  const float* d_mp_max_dist;
+  const uint8_t* d_mp_desc;
+  int32_t* d_match;
+  int32_t* d_nmatches;
+} orbm_kf_device_batch;
+int orbm_search_by_projection_kf_batch_device(const orbpl_camera* cam, const float* scale_factors,
+                                              int nlevels, const orbm_kf_device_batch* b,
+                                              int batch, float th, int orb_dist, int check_ori,
+                                              void* stream);
+
+/* ------------------------------------------------------------------------
  * Optimizer::PoseOptimization / PoseOptimizationWithLines
  * (Optimizer.cc:375-619, 2132-2486): 4 rounds x 10 Levenberg-Marquardt
  * iterations on one SE3 vertex, Huber kernel in rounds 0-2, chi2 outlier

@@ -447,6 +447,11 @@ def _declare_track(L):
     L.orbpl_tracker_get_map_keyframes.argtypes = [vp, i, vp, vp, i, vp, ip]
     L.orbpl_tracker_get_map_points.argtypes = [vp, i, i, vp, vp, vp, vp, vp, ip]
     L.orbpl_tracker_get_map_lines.argtypes = [vp, i, i, vp, vp, vp, ip]
+    L.orbm_search_by_projection_kf.argtypes = [vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp, vp, vp,
+                                               C.c_float, i, i, vp, ip]
+    L.orbm_search_by_projection_kf_batch_device.argtypes = [vp, vp, i, vp, i, C.c_float, i, i, vp]
+    L.orbkf_detect_reloc.argtypes = [vp, i, i]
+    L.orbkf_detect_reloc_batch_device.argtypes = [vp, i, i, vp]
 
 
 _declare_orig = _declare
@@ -551,6 +556,37 @@ class ORBmatcher:
             arr(track["view_cos"], np.float32), arr(mp_desc, np.uint8), arr(mp_nobs, np.int32),
             None if cur_nobs is None else arr(cur_nobs, np.int32), float(th), float(self.nnratio),
             _ptr(match), C.byref(nm)), "orbm_search_by_projection_local")
+        return match[:n].copy(), nm.value
+
+    def SearchByProjectionKeyFrame(self, camera, scale_factors, cur, cur_has_mp, kf, th, ORBdist):
+        """SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)
+        (ORBmatcher.cc:1891-2024), Tracking::Relocalization's matcher.
+        ``cur``: dict Tcw, kps_un, desc; ``cur_has_mp[i]``: keypoint i holds a
+        map point on entry; ``kf``: dict of per-feature arrays angle, valid
+        (map point exists and is not bad), found (in sAlreadyFound), mp_xyz,
+        mp_min_dist / mp_max_dist (raw mfMinDistance / mfMaxDistance), mp_desc.
+        Returns (match, nmatches): match[i] = keyframe feature index or -1."""
+        sf = _c(scale_factors, np.float32)
+        keep = []
+
+        def arr(a, dt):
+            a = _c(a, dt)
+            keep.append(a)
+            return _ptr(a)
+
+        n = len(cur["kps_un"])
+        nkf = len(kf["angle"])
+        mc = MatchCurrent(n, arr(cur["Tcw"], np.float32), arr(cur["kps_un"], KP_DTYPE),
+                          arr(cur["desc"], np.uint8), None)
+        match = np.zeros(max(1, n), np.int32)
+        nm = C.c_int(0)
+        check(lib().orbm_search_by_projection_kf(
+            C.byref(camera), _ptr(sf), len(sf), C.byref(mc), arr(cur_has_mp, np.uint8), nkf,
+            arr(kf["angle"], np.float32), arr(kf["valid"], np.uint8), arr(kf["found"], np.uint8),
+            arr(kf["mp_xyz"], np.float32), arr(kf["mp_min_dist"], np.float32),
+            arr(kf["mp_max_dist"], np.float32), arr(kf["mp_desc"], np.uint8), float(th),
+            int(ORBdist), int(self.checkOri), _ptr(match), C.byref(nm)),
+            "orbm_search_by_projection_kf")
         return match[:n].copy(), nm.value
 
 
@@ -1293,3 +1329,124 @@ class ORBVocabulary:
         if getattr(self, "_h", None) and _lib is not None:
             _lib.orbv_destroy(self._h)
             self._h = None
+
+
+# ---------------------------------------------------------------------------
+# KeyFrameDatabase::DetectRelocalizationCandidates (KeyFrameDatabase.cc:274-412)
+# ---------------------------------------------------------------------------
+KFDB_MAX_KEYFRAMES = 64
+KFDB_MAX_WORDS = 4096
+KFDB_COVISIBLES = 10
+
+
+class KfdbProblem(C.Structure):
+    _fields_ = [("nkf", C.c_int32), ("kf_off", C.c_void_p), ("kf_words", C.c_void_p),
+                ("kf_vals", C.c_void_p), ("covis", C.c_void_p), ("reloc_score", C.c_void_p),
+                ("nq_words", C.c_int32), ("q_words", C.c_void_p), ("q_vals", C.c_void_p),
+                ("cand", C.c_void_p), ("ncand", C.c_void_p), ("common_words", C.c_void_p)]
+
+
+class KfdbDeviceBatch(C.Structure):
+    _fields_ = [("d_nkf", C.c_void_p), ("d_kf_off", C.c_void_p), ("d_kf_words", C.c_void_p),
+                ("d_kf_vals", C.c_void_p), ("ent_pitch", C.c_int64), ("d_covis", C.c_void_p),
+                ("d_reloc_score", C.c_void_p), ("d_q_n", C.c_void_p), ("d_q_words", C.c_void_p),
+                ("d_q_vals", C.c_void_p), ("q_pitch", C.c_int64), ("d_cand", C.c_void_p),
+                ("d_ncand", C.c_void_p), ("d_common_words", C.c_void_p)]
+
+
+class MatchKfDeviceBatch(C.Structure):
+    _fields_ = [("kp_pitch", C.c_int32), ("d_cur_n", C.c_void_p), ("d_Tcw", C.c_void_p),
+                ("d_cur_kps_un", C.c_void_p), ("d_cur_desc", C.c_void_p),
+                ("d_cur_has_mp", C.c_void_p), ("kf_pitch", C.c_int32), ("d_kf_n", C.c_void_p),
+                ("d_kf_angle", C.c_void_p), ("d_kf_valid", C.c_void_p), ("d_kf_found", C.c_void_p),
+                ("d_mp_xyz", C.c_void_p), ("d_mp_min_dist", C.c_void_p),
+                ("d_mp_max_dist", C.c_void_p), ("d_mp_desc", C.c_void_p), ("d_match", C.c_void_p),
+                ("d_nmatches", C.c_void_p)]
+
+
+def detect_reloc_batch(problems, scoring=0):
+    """DetectRelocalizationCandidates for a list of independent (database,
+    query) problems in one launch. Each problem is a dict: ``kf_bows`` = the
+    database's BowVectors [(words u32 ascending, values f64), ...] in add()
+    order, ``covis`` = per keyframe the database indices of
+    GetBestCovisibilityKeyFrames(10) (-1 or missing: none), ``reloc_score`` =
+    mRelocScore per keyframe (float32, persistent state), ``q_words`` /
+    ``q_vals`` = the query's BowVector. Returns per problem a dict: ``cand``
+    (database indices in the reference's order), ``common_words``
+    (mnRelocWords), ``reloc_score`` (updated copy)."""
+    nq = len(problems)
+    arr = (KfdbProblem * max(1, nq))()
+    keep, outs = [], []
+    for p, pr in enumerate(problems):
+        bows = pr["kf_bows"]
+        nkf = len(bows)
+        off = np.zeros(nkf + 1, np.int32)
+        for k, (w, _) in enumerate(bows):
+            off[k + 1] = off[k] + len(w)
+        kw = (np.concatenate([_c(w, np.uint32) for w, _ in bows]) if nkf
+              else np.zeros(0, np.uint32))
+        kv = (np.concatenate([_c(v, np.float64) for _, v in bows]) if nkf
+              else np.zeros(0, np.float64))
+        kw, kv = _c(kw, np.uint32), _c(kv, np.float64)
+        cov = np.full((max(1, nkf), KFDB_COVISIBLES), -1, np.int32)
+        for k, lst in enumerate(pr.get("covis", [])[:nkf]):
+            lst = list(lst)[:KFDB_COVISIBLES]
+            cov[k, :len(lst)] = lst
+        rs = np.zeros(max(1, nkf), np.float32)
+        if pr.get("reloc_score") is not None:
+            rs[:nkf] = _c(pr["reloc_score"], np.float32)
+        qw, qv = _c(pr["q_words"], np.uint32), _c(pr["q_vals"], np.float64)
+        cand = np.zeros(KFDB_MAX_KEYFRAMES, np.int32)
+        nc = np.zeros(1, np.int32)
+        cw = np.zeros(max(1, nkf), np.int32)
+        keep += [off, kw, kv, cov, rs, qw, qv, cand, nc, cw]
+        arr[p] = KfdbProblem(nkf, _ptr(off), _ptr(kw), _ptr(kv), _ptr(cov), _ptr(rs), len(qw),
+                             _ptr(qw), _ptr(qv), _ptr(cand), _ptr(nc), _ptr(cw))
+        outs.append((nkf, cand, nc, cw, rs))
+    check(lib().orbkf_detect_reloc(C.byref(arr), nq, int(scoring)), "orbkf_detect_reloc")
+    return [dict(cand=cand[:int(nc[0])].copy(), common_words=cw[:nkf].copy(),
+                 reloc_score=rs[:nkf].copy()) for nkf, cand, nc, cw, rs in outs]
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM2::KeyFrameDatabase reduced to relocalisation: the keyframes'
+    BowVectors in add() order, their ordered covisibles and the persistent
+    mRelocScore (starts at 0.0f). Keyframes are named by the
+    index add() returned; erase() leaves the other indices unchanged."""
+
+    def __init__(self, scoring=0):
+        self.scoring = scoring
+        self.clear()
+
+    def clear(self):
+        self._bows, self._covis, self._score, self._alive = [], [], [], []
+
+    def add(self, bow_words, bow_vals):
+        self._bows.append((_c(bow_words, np.uint32).copy(), _c(bow_vals, np.float64).copy()))
+        self._covis.append([])
+        self._score.append(np.float32(0.0))
+        self._alive.append(True)
+        return len(self._bows) - 1
+
+    def erase(self, idx):
+        self._alive[idx] = False
+
+    def set_covisibles(self, idx, covisibles):
+        """GetBestCovisibilityKeyFrames(10) of keyframe idx, as add() indices"""
+        self._covis[idx] = [int(k) for k in covisibles][:KFDB_COVISIBLES]
+
+    def reloc_score(self, idx):
+        return self._score[idx]
+
+    def DetectRelocalizationCandidates(self, bow_words, bow_vals):
+        live = [k for k, a in enumerate(self._alive) if a]
+        pos = {k: j for j, k in enumerate(live)}
+        pr = dict(kf_bows=[self._bows[k] for k in live],
+                  covis=[[pos.get(c, -1) for c in self._covis[k]] for k in live],
+                  reloc_score=np.array([self._score[k] for k in live], np.float32),
+                  q_words=bow_words, q_vals=bow_vals)
+        out = detect_reloc_batch([pr], self.scoring)[0]
+        for j, k in enumerate(live):
+            self._score[k] = out["reloc_score"][j]
+        self.last_common_words = {k: int(out["common_words"][j]) for j, k in enumerate(live)}
+        return [live[j] for j in out["cand"]]

@@ -27,6 +27,7 @@
 #include "track_common.h"
 #include "track_kernels.h"
 #include "orbpl_runtime.h"
+#include "reloc_kernels.h"
 
 namespace orbpl {
 
@@ -847,6 +848,373 @@ void launch_trk_bow(const TrkArgs& a, int nstreams, hipStream_t s) {
     hipLaunchKernelGGL(k_trk_bow<1024>, dim3(grid), dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL(k_trk_bow<kBowMax>, dim3(grid), dim3(256), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------
+// ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF,
+// const set<MapPoint*>& sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1891-2024),
+// the matcher of Tracking::Relocalization's refinement (Tracking.cc:2195-2230).
+// One 256-thread workgroup per problem, k_match_last's scheme:
+//   grid     - the current frame's 64x48 grid in LDS, cells column-major and
+//              each cell's keypoints in index order = GetFeaturesInArea's scan
+//   phase A  - every keyframe map point in parallel: projection, distance
+//              range, PredictScale, window, and its first kTopK candidates in
+//              (distance, scan position) order among the keypoints that hold no
+//              map point on entry and lie within ORBdist
+//   phase B  - wave 0, keyframe points in index order. A keypoint that holds a
+//              map point is skipped whether it held one on entry or was
+//              claimed earlier in the call, so every accepted point claims its
+//              keypoint and a point's outcome under the earlier claims is the
+//              first unclaimed entry of its list. Chunks of 64 commit up to
+//              the first lane whose choice an earlier lane of the chunk takes
+//              (or whose list ran out while more candidates exist: that lane
+//              scans again against the claims once the lanes before it have
+//              committed); the rest of the chunk repeats.
+//   phase C  - rotation histogram, ComputeThreeMaxima, removal.
+// The reference has no invzc < 0 test here; a projection that is not a number
+// (z = 0) is rejected (the reference converts it to a cell index: undefined).
+// ---------------------------------------------------------------------------
+namespace {
+
+template <int KMAX>
+struct KfShared {
+  int cell_start[kGridCols * kGridRows + 1];
+  uint16_t items[KMAX];
+  float2 xy[KMAX];
+  float ang[KMAX];
+  int8_t oct[KMAX];
+  int16_t gc[KMAX];
+  int top[KMAX * kTopK];     // per keyframe point: dist << 16 | keypoint, sorted; -1 empty;
+                             // during the grid build: per-cell fill counters
+  uint8_t ntop[KMAX];        // candidates within ORBdist (saturating)
+  int bin[KMAX];             // per keyframe point: histogram bin of its match, else -1
+  int sel[KMAX];             // per keyframe point: the keypoint it claimed
+  int mpw[KMAX];             // per keypoint: the keyframe point that claimed it
+  int fc[KMAX];              // phase B: first lane choosing a keypoint (INT_MAX: none)
+  uint32_t claimed[KMAX / 32];   // keypoint holds a map point (on entry or claimed)
+  uint32_t removed[KMAX / 32];
+  int hist[32];
+  int wsum[4];
+  int misc[8];
+};
+static_assert(1024 * kTopK >= kGridCols * kGridRows, "top[] doubles as cell fill counters");
+
+struct KfProj {
+  bool ok;
+  float u, v, radius;
+  int minLevel, maxLevel;
+  int cx0, cx1, cy0, cy1;
+};
+
+__device__ KfProj kf_project(const TrackConsts& c, const MatchKfArgs& a, const float* Tc,
+                             const float* Ow, long long j) {
+  KfProj p;
+  p.ok = false;
+  const float X[3] = {a.mp_xyz[3 * j], a.mp_xyz[3 * j + 1], a.mp_xyz[3 * j + 2]};
+  float x3Dc[3];
+  gemm_R_x_plus_t(Tc, X, x3Dc);
+  const float xc = x3Dc[0], yc = x3Dc[1];
+  const float invzc = (float)(1.0 / (double)x3Dc[2]);
+  const float u = c.fx * xc * invzc + c.cx;
+  const float v = c.fy * yc * invzc + c.cy;
+  if (u < c.minX || u > c.maxX) return p;
+  if (v < c.minY || v > c.maxY) return p;
+  if (u != u || v != v) return p;
+  const float PO[3] = {X[0] - Ow[0], X[1] - Ow[1], X[2] - Ow[2]};
+  // cv::norm (P16): double squares, one rounding
+  const float dist3D =
+      (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
+  const float maxDistance = 1.2f * a.mp_max_dist[j], minDistance = 0.8f * a.mp_min_dist[j];
+  if (dist3D < minDistance || dist3D > maxDistance) return p;
+  int lev = 0;
+  if (c.nlevels > 1) {   // MapPoint::PredictScale (MapPoint.cc:416-431, P15)
+    const float ratio = a.mp_max_dist[j] / dist3D;
+    lev = (int)ceilf((float)lsdm::log_((double)ratio) / a.log_scale);
+    if (lev < 0) lev = 0;
+    else if (lev >= c.nlevels) lev = c.nlevels - 1;
+  }
+  const float r = a.th * c.scale[lev];
+  p.u = u;
+  p.v = v;
+  p.radius = r;
+  p.minLevel = lev - 1;
+  p.maxLevel = lev + 1;
+  p.cx0 = max(0, (int)floorf((u - c.minX - r) * c.gridInvW));
+  p.cx1 = min(kGridCols - 1, (int)ceilf((u - c.minX + r) * c.gridInvW));
+  p.cy0 = max(0, (int)floorf((v - c.minY - r) * c.gridInvH));
+  p.cy1 = min(kGridRows - 1, (int)ceilf((v - c.minY + r) * c.gridInvH));
+  if (p.cx0 >= kGridCols || p.cx1 < 0 || p.cy0 >= kGridRows || p.cy1 < 0) return p;
+  p.ok = true;
+  return p;
+}
+
+// GetFeaturesInArea(u, v, radius, level - 1, level + 1) and the candidate loop
+// (ORBmatcher.cc:1952-1977) against the current claims: the candidates within
+// `orbd` in (distance, scan position) order, the first kTopK into tk, the
+// count returned
+template <int KMAX>
+__device__ int kf_scan(const KfShared<KMAX>& S, const KfProj& p, const uint8_t* dMP,
+                       const uint8_t* cdesc, int orbd, int* tk) {
+  int cnt = 0;
+#pragma unroll
+  for (int q = 0; q < kTopK; q++) tk[q] = -1;
+  const float r = p.radius;
+  for (int ix = p.cx0; ix <= p.cx1; ix++) {
+    const int b = S.cell_start[ix * kGridRows + p.cy0];
+    const int e = S.cell_start[ix * kGridRows + p.cy1 + 1];
+    for (int q = b; q < e; q++) {
+      const int j = S.items[q];
+      const int oc = S.oct[j];
+      // bCheckLevels holds: maxLevel = level + 1 >= 0
+      if (oc < p.minLevel || oc > p.maxLevel) continue;
+      const float2 xy = S.xy[j];
+      if (!(fabsf(xy.x - p.u) < r && fabsf(xy.y - p.v) < r)) continue;
+      if ((S.claimed[j >> 5] >> (j & 31)) & 1u) continue;
+      const int dist = hamming32l(dMP, cdesc + (long long)j * 32);
+      if (dist > orbd) continue;
+      cnt++;
+      int v = (dist << 16) | j;
+      // stable insertion: equal distances keep scan order
+      bool ins = false;
+#pragma unroll
+      for (int q2 = 0; q2 < kTopK; q2++) {
+        const int cur = tk[q2];
+        if (ins || cur < 0 || (v >> 16) < (cur >> 16)) {
+          tk[q2] = v;
+          v = cur;
+          ins = true;
+          if (v < 0) break;
+        }
+      }
+    }
+  }
+  return cnt;
+}
+
+}  // namespace
+
+template <int KMAX>
+__global__ void __launch_bounds__(256) k_match_kf(TrackConsts c, MatchKfArgs a) {
+  constexpr int NT = 256;
+  extern __shared__ char smem_kf[];
+  KfShared<KMAX>& S = *reinterpret_cast<KfShared<KMAX>*>(smem_kf);
+  const int s = blockIdx.x, t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int n = min(max(a.cur_n[s], 0), min(KMAX, a.kp_pitch));
+  const int nk = min(max(a.kf_n[s], 0), min(KMAX, a.kf_pitch));
+  const long long cb = (long long)s * a.kp_pitch, kb = (long long)s * a.kf_pitch;
+  const KeyPointD* ck = a.cur_kps_un + cb;
+  const uint8_t* cdesc = a.cur_desc + cb * 32;
+  const float* Tc = a.Tcw + (long long)s * a.pose_stride;
+  // the smallest distance a candidate can have is 0 and a distance of 256 never
+  // beats the initial bestDist = 256, so ORBdist acts within [-1, 255]
+  const int orbd = min(max(a.orb_dist, -1), 255);
+  // ---- current frame into LDS + grid (AssignFeaturesToGrid, Frame.cc:265-287) ----
+  for (int i = t; i < kGridCols * kGridRows; i += NT) S.cell_start[i] = 0;
+  for (int i = t; i < KMAX / 32; i += NT) {
+    S.claimed[i] = 0;
+    S.removed[i] = 0;
+  }
+  if (t < 32) S.hist[t] = 0;
+  __syncthreads();
+  for (int i = t; i < n; i += NT) {
+    const KeyPointD k = ck[i];
+    S.xy[i] = make_float2(k.x, k.y);
+    S.ang[i] = k.angle;
+    S.oct[i] = (int8_t)k.octave;
+    S.mpw[i] = -1;
+    S.fc[i] = 0x7fffffff;
+    // Frame::PosInGrid (Frame.cc:527-538)
+    const int px = (int)roundf((k.x - c.minX) * c.gridInvW);
+    const int py = (int)roundf((k.y - c.minY) * c.gridInvH);
+    const int g = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? -1 : px * kGridRows + py;
+    S.gc[i] = (int16_t)g;
+    if (g >= 0) atomicAdd(&S.cell_start[g], 1);
+    if (a.cur_has_mp[cb + i]) atomicOr(&S.claimed[i >> 5], 1u << (i & 31));
+  }
+  __syncthreads();
+  {  // exclusive scan of the 3072 cell counts
+    constexpr int kPer = (kGridCols * kGridRows) / NT;
+    int loc[kPer];
+    int sum = 0;
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+      loc[k] = S.cell_start[t * kPer + k];
+      sum += loc[k];
+    }
+    int incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int u = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += u;
+    }
+    if (lane == 63) S.wsum[wave] = incl;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; w++) base += S.wsum[w];
+    int run = base + incl - sum;
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+      S.cell_start[t * kPer + k] = run;
+      S.top[t * kPer + k] = run;   // fill counter
+      run += loc[k];
+    }
+    if (t == NT - 1) S.cell_start[kGridCols * kGridRows] = run;
+    __syncthreads();
+  }
+  for (int i = t; i < n; i += NT) {
+    const int g = S.gc[i];
+    if (g >= 0) S.items[atomicAdd(&S.top[g], 1)] = (uint16_t)i;
+  }
+  __syncthreads();
+  // mGrid[ix][iy] holds its keypoints in increasing index order
+  for (int cell = t; cell < kGridCols * kGridRows; cell += NT) {
+    const int b = S.cell_start[cell], e = S.cell_start[cell + 1];
+    for (int q = b + 1; q < e; q++) {
+      const uint16_t v = S.items[q];
+      int r = q - 1;
+      while (r >= b && S.items[r] > v) {
+        S.items[r + 1] = S.items[r];
+        r--;
+      }
+      S.items[r + 1] = v;
+    }
+  }
+  __syncthreads();
+  float Ow[3];
+  gemm_neg_Rt_t(Tc, Ow);
+  // ---- phase A ----
+  for (int i = t; i < nk; i += NT) {
+    int tk[kTopK] = {-1, -1, -1, -1};
+    int cnt = 0;
+    if (a.kf_valid[kb + i] && !a.kf_found[kb + i]) {
+      const KfProj p = kf_project(c, a, Tc, Ow, kb + i);
+      if (p.ok) cnt = kf_scan(S, p, a.mp_desc + (kb + i) * 32, cdesc, orbd, tk);
+    }
+#pragma unroll
+    for (int q = 0; q < kTopK; q++) S.top[i * kTopK + q] = tk[q];
+    S.ntop[i] = (uint8_t)min(cnt, 255);
+    S.bin[i] = -1;
+    S.sel[i] = -1;
+  }
+  __syncthreads();
+  // ---- phase B (wave 0): the reference's loop over the keyframe's points ----
+  if (wave == 0) {
+    int acc = 0;
+    for (int base = 0; base < nk; base += 64) {
+      const int i = base + lane;
+      const int nt = i < nk ? (int)S.ntop[i] : 0;
+      const int ntk = min(nt, kTopK);
+      bool decided = nt == 0;
+      int p = 0, choice = -1;   // >= 0 keypoint, -1 none, -2 the list ran out: scan again
+      auto commit = [&](int k) {
+        S.mpw[k] = i;
+        atomicOr(&S.claimed[k >> 5], 1u << (k & 31));
+        float rot = a.kf_angle[kb + i] - S.ang[k];
+        if (rot < 0.0f) rot += 360.0f;
+        int b = (int)roundf(rot * (30 / 360.0f));
+        if (b == 30) b = 0;
+        S.bin[i] = b;
+        S.sel[i] = k;
+        acc++;
+      };
+      while (true) {
+        const bool und = !decided;
+        if (und) {
+          while (p < ntk) {
+            const int k = S.top[i * kTopK + p] & 0xFFFF;
+            if (!((S.claimed[k >> 5] >> (k & 31)) & 1u)) break;
+            p++;
+          }
+          choice = p < ntk ? (S.top[i * kTopK + p] & 0xFFFF) : (nt > kTopK ? -2 : -1);
+        }
+        const bool cq = und && choice >= 0;
+        if (cq) atomicMin(&S.fc[choice], lane);
+        lds_wave_sync();
+        const bool coll = und && (choice == -2 || (choice >= 0 && S.fc[choice] < lane));
+        lds_wave_sync();
+        if (cq) S.fc[choice] = 0x7fffffff;
+        lds_wave_sync();
+        const unsigned long long cm = __ballot(coll);
+        const int lc = cm ? __ffsll((long long)cm) - 1 : 64;
+        if (und && lane < lc) {
+          if (choice >= 0) commit(choice);
+          decided = true;
+        }
+        if (lc == 64) break;
+        lds_wave_sync();
+        if (lane == lc && choice == -2) {
+          int tk[kTopK];
+          const KfProj pj = kf_project(c, a, Tc, Ow, kb + i);
+          if (pj.ok && kf_scan(S, pj, a.mp_desc + (kb + i) * 32, cdesc, orbd, tk) > 0)
+            commit(tk[0] & 0xFFFF);
+          decided = true;
+        }
+        lds_wave_sync();
+      }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) S.misc[0] = acc;
+  }
+  __syncthreads();
+  int nmatches = S.misc[0];
+  // ---- phase C: rotation consistency (ORBmatcher.cc:2001-2021, 2035-2077) ----
+  if (a.check_ori) {
+    for (int i = t; i < nk; i += NT)
+      if (S.bin[i] >= 0) atomicAdd(&S.hist[S.bin[i]], 1);
+    __syncthreads();
+    if (t == 0) {
+      int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+      for (int i = 0; i < 30; i++) {
+        const int sz = S.hist[i];
+        if (sz > max1) {
+          max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i;
+        } else if (sz > max2) {
+          max3 = max2; max2 = sz; ind3 = ind2; ind2 = i;
+        } else if (sz > max3) {
+          max3 = sz; ind3 = i;
+        }
+      }
+      if (max2 < 0.1f * (float)max1) {
+        ind2 = -1; ind3 = -1;
+      } else if (max3 < 0.1f * (float)max1) {
+        ind3 = -1;
+      }
+      S.misc[1] = ind1; S.misc[2] = ind2; S.misc[3] = ind3;
+      S.misc[4] = 0;
+    }
+    __syncthreads();
+    const int ind1 = S.misc[1], ind2 = S.misc[2], ind3 = S.misc[3];
+    int nrem = 0;
+    for (int i = t; i < nk; i += NT) {
+      const int b = S.bin[i];
+      if (b >= 0 && b != ind1 && b != ind2 && b != ind3) {
+        const int k = S.sel[i];
+        atomicOr(&S.removed[k >> 5], 1u << (k & 31));
+        nrem++;
+      }
+    }
+    if (nrem) atomicAdd(&S.misc[4], nrem);
+    __syncthreads();
+    nmatches -= S.misc[4];
+  }
+  for (int i = t; i < n; i += NT) {
+    int m = S.mpw[i];
+    if (a.check_ori && ((S.removed[i >> 5] >> (i & 31)) & 1u)) m = -1;
+    a.match[cb + i] = m;
+  }
+  if (t == 0) a.nmatches[(long long)s * a.nm_stride] = nmatches;
+}
+
+void launch_match_kf(const TrackConsts& c, const MatchKfArgs& a, int batch, hipStream_t s) {
+  if (batch <= 0) return;
+  if (max(a.kp_pitch, a.kf_pitch) <= 1024) {
+    set_smem_attr((const void*)k_match_kf<1024>, sizeof(KfShared<1024>));
+    hipLaunchKernelGGL(k_match_kf<1024>, dim3(batch), dim3(256), sizeof(KfShared<1024>), s, c, a);
+  } else {
+    set_smem_attr((const void*)k_match_kf<2048>, sizeof(KfShared<2048>));
+    hipLaunchKernelGGL(k_match_kf<2048>, dim3(batch), dim3(256), sizeof(KfShared<2048>), s, c, a);
+  }
 }
 
 }  // namespace orbpl

@@ -18,6 +18,7 @@
 #include "lsd_kernels.h"
 #include "lsd_math.h"
 #include "map_kernels.h"
+#include "reloc_kernels.h"
 
 using namespace orbpl;
 
@@ -588,6 +589,119 @@ int orbm_search_by_bow(int nkf, const int32_t* kf_node, const uint8_t* kf_valid,
   HIP_CHECK(hipGetLastError());
   if (nf) HIP_CHECK(hipMemcpy(match, dm.p, F * 4, hipMemcpyDeviceToHost));
   HIP_CHECK(hipMemcpy(nmatches, dnm.p, 4, hipMemcpyDeviceToHost));
+  return ORBPL_OK;
+}
+
+// Frame::mfLogScaleFactor = log(mfScaleFactor) (P15); mvScaleFactors[1] is
+// 1.0f * mfScaleFactor. One level: PredictScale always gives level 0.
+static float log_scale_of(const float* scale_factors, int nlevels) {
+  return nlevels > 1 ? (float)lsdm::log_((double)scale_factors[1]) : 1.0f;
+}
+
+int orbm_search_by_projection_kf_batch_device(const orbpl_camera* cam, const float* scale_factors,
+                                              int nlevels, const orbm_kf_device_batch* b,
+                                              int batch, float th, int orb_dist, int check_ori,
+                                              void* stream) {
+  if (!cam || !scale_factors || !b || batch < 0) return arg_fail("bad argument");
+  if (b->kp_pitch < 1 || b->kf_pitch < 1 || b->kp_pitch > kMatchMaxKp || b->kf_pitch > kMatchMaxKp)
+    return arg_fail("pitch outside [1, 2048] (the matcher capacity)");
+  if (!b->d_cur_n || !b->d_Tcw || !b->d_cur_kps_un || !b->d_cur_desc || !b->d_cur_has_mp ||
+      !b->d_kf_n || !b->d_kf_angle || !b->d_kf_valid || !b->d_kf_found || !b->d_mp_xyz ||
+      !b->d_mp_min_dist || !b->d_mp_max_dist || !b->d_mp_desc || !b->d_match || !b->d_nmatches)
+    return arg_fail("NULL device array");
+  TrackConsts c;
+  int rc = make_consts(cam, scale_factors, nullptr, nlevels, &c);
+  if (rc) return rc;
+  if (batch == 0) return ORBPL_OK;
+  MatchKfArgs a{};
+  a.cur_kps_un = reinterpret_cast<const KeyPointD*>(b->d_cur_kps_un);
+  a.cur_desc = b->d_cur_desc;
+  a.cur_has_mp = b->d_cur_has_mp;
+  a.cur_n = b->d_cur_n;
+  a.kp_pitch = b->kp_pitch;
+  a.kf_angle = b->d_kf_angle;
+  a.kf_valid = b->d_kf_valid;
+  a.kf_found = b->d_kf_found;
+  a.mp_xyz = b->d_mp_xyz;
+  a.mp_min_dist = b->d_mp_min_dist;
+  a.mp_max_dist = b->d_mp_max_dist;
+  a.mp_desc = b->d_mp_desc;
+  a.kf_n = b->d_kf_n;
+  a.kf_pitch = b->kf_pitch;
+  a.Tcw = b->d_Tcw;
+  a.pose_stride = 16;
+  a.match = b->d_match;
+  a.nmatches = b->d_nmatches;
+  a.nm_stride = 1;
+  a.th = th;
+  a.orb_dist = orb_dist;
+  a.check_ori = check_ori;
+  a.log_scale = log_scale_of(scale_factors, nlevels);
+  launch_match_kf(c, a, batch, (hipStream_t)stream);
+  HIP_CHECK(hipGetLastError());
+  return ORBPL_OK;
+}
+
+int orbm_search_by_projection_kf(const orbpl_camera* cam, const float* scale_factors, int nlevels,
+                                 const orbpl_match_current* cur, const uint8_t* cur_has_mp,
+                                 int nkf, const float* kf_angle, const uint8_t* kf_valid,
+                                 const uint8_t* kf_found, const float* mp_xyz,
+                                 const float* mp_min_dist, const float* mp_max_dist,
+                                 const uint8_t* mp_desc, float th, int orb_dist, int check_ori,
+                                 int32_t* match, int* nmatches) {
+  if (!cam || !scale_factors || !cur || !nmatches) return arg_fail("NULL argument");
+  const int n = cur->n;
+  if (n < 0 || nkf < 0 || n > kMatchMaxKp || nkf > kMatchMaxKp)
+    return arg_fail("keypoint count exceeds the matcher capacity (2048)");
+  if (!cur->Tcw || (n > 0 && (!cur->kps_un || !cur->desc || !cur_has_mp || !match)) ||
+      (nkf > 0 && (!kf_angle || !kf_valid || !kf_found || !mp_xyz || !mp_min_dist ||
+                   !mp_max_dist || !mp_desc)))
+    return arg_fail("NULL feature arrays");
+  const size_t N = std::max(1, n), K = std::max(1, nkf);
+  DBuf d_n, d_T, d_ku, d_cd, d_ch, d_kn, d_ka, d_kv, d_kf, d_x, d_mn, d_mx, d_md, d_m, d_nm;
+  HIP_CHECK(d_n.alloc(4));
+  HIP_CHECK(d_T.alloc(64));
+  HIP_CHECK(d_ku.alloc(N * sizeof(KeyPointD)));
+  HIP_CHECK(d_cd.alloc(N * 32));
+  HIP_CHECK(d_ch.alloc(N));
+  HIP_CHECK(d_kn.alloc(4));
+  HIP_CHECK(d_ka.alloc(K * 4));
+  HIP_CHECK(d_kv.alloc(K));
+  HIP_CHECK(d_kf.alloc(K));
+  HIP_CHECK(d_x.alloc(K * 12));
+  HIP_CHECK(d_mn.alloc(K * 4));
+  HIP_CHECK(d_mx.alloc(K * 4));
+  HIP_CHECK(d_md.alloc(K * 32));
+  HIP_CHECK(d_m.alloc(N * 4));
+  HIP_CHECK(d_nm.alloc(4));
+  HIP_CHECK(hipMemcpy(d_n.p, &n, 4, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_T.p, cur->Tcw, 64, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(d_kn.p, &nkf, 4, hipMemcpyHostToDevice));
+  if (n) {
+    HIP_CHECK(hipMemcpy(d_ku.p, cur->kps_un, (size_t)n * sizeof(KeyPointD), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_cd.p, cur->desc, (size_t)n * 32, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_ch.p, cur_has_mp, (size_t)n, hipMemcpyHostToDevice));
+  }
+  if (nkf) {
+    HIP_CHECK(hipMemcpy(d_ka.p, kf_angle, (size_t)nkf * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_kv.p, kf_valid, (size_t)nkf, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_kf.p, kf_found, (size_t)nkf, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_x.p, mp_xyz, (size_t)nkf * 12, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_mn.p, mp_min_dist, (size_t)nkf * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_mx.p, mp_max_dist, (size_t)nkf * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_md.p, mp_desc, (size_t)nkf * 32, hipMemcpyHostToDevice));
+  }
+  const orbm_kf_device_batch b{(int32_t)N, d_n.as<int32_t>(), d_T.as<float>(),
+                               d_ku.as<orbpl_keypoint>(), d_cd.as<uint8_t>(), d_ch.as<uint8_t>(),
+                               (int32_t)K, d_kn.as<int32_t>(), d_ka.as<float>(), d_kv.as<uint8_t>(),
+                               d_kf.as<uint8_t>(), d_x.as<float>(), d_mn.as<float>(),
+                               d_mx.as<float>(), d_md.as<uint8_t>(), d_m.as<int32_t>(),
+                               d_nm.as<int32_t>()};
+  int rc = orbm_search_by_projection_kf_batch_device(cam, scale_factors, nlevels, &b, 1, th,
+                                                     orb_dist, check_ori, scratch_stream());
+  if (rc) return rc;
+  if (n) HIP_CHECK(hipMemcpy(match, d_m.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(nmatches, d_nm.p, 4, hipMemcpyDeviceToHost));
   return ORBPL_OK;
 }
 

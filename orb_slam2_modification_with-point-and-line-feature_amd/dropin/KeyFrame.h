@@ -4,8 +4,11 @@
 // matches and FeatureVector (ORBmatcher::SearchByBoW, ORBmatcher.cc:247-410),
 // its key lines, line descriptors and map lines (LineMatcher::
 // SearchByProjection(Frame&, KeyFrame*), LineMatcher.cpp:527-721) - copied
-// from the Frame it is made of, as KeyFrame::KeyFrame(Frame&, ...) does. The
-// covisibility graph, spanning tree and map bookkeeping stay the caller's.
+// from the Frame it is made of, as KeyFrame::KeyFrame(Frame&, ...) does; the
+// relocalisation state KeyFrameDatabase::DetectRelocalizationCandidates keeps
+// in it (mnRelocQuery, mnRelocWords, mRelocScore) and the ordered covisibles
+// it reads, set by the caller (SetOrderedCovisibles). The covisibility graph,
+// spanning tree and map bookkeeping stay the caller's.
 #pragma once
 #include <stdexcept>
 #include <vector>
@@ -37,10 +40,27 @@ class KeyFrame {
   std::vector<MapLine*> GetMapLineMatches() const { return mvpMapLines; }
   MapPoint* GetMapPoint(const size_t& idx) const { return mvpMapPoints[idx]; }
   cv::Mat GetPose() const { return Tcw.clone(); }
+  bool isBad() const { return mbBad; }
+  void SetBadFlag() { mbBad = true; }
+  // KeyFrame::GetBestCovisibilityKeyFrames (KeyFrame.cc:250-258): the first N
+  // of the ordered covisibles, which the caller's covisibility graph sets
+  // (mvpOrderedConnectedKeyFrames after UpdateBestCovisibles)
+  void SetOrderedCovisibles(const std::vector<KeyFrame*>& v) { mvpOrderedConnectedKeyFrames = v; }
+  std::vector<KeyFrame*> GetBestCovisibilityKeyFrames(const int& N) const {
+    if ((int)mvpOrderedConnectedKeyFrames.size() < N) return mvpOrderedConnectedKeyFrames;
+    return std::vector<KeyFrame*>(mvpOrderedConnectedKeyFrames.begin(),
+                                  mvpOrderedConnectedKeyFrames.begin() + N);
+  }
 
   static long unsigned int nNextId;
   long unsigned int mnId = 0;
   const long unsigned int mnFrameId;
+  // KeyFrameDatabase::DetectRelocalizationCandidates' per-keyframe state
+  // (KeyFrame.h:226-228). The reference never initialises mRelocScore
+  // (KeyFrame.cc:32); pinned: it starts at 0.0f
+  long unsigned int mnRelocQuery = 0;
+  int mnRelocWords = 0;
+  float mRelocScore = 0.0f;
   const int N, NL;
   const std::vector<cv::KeyPoint> mvKeys, mvKeysUn;
   const std::vector<float> mvuRight, mvDepth;
@@ -56,6 +76,8 @@ class KeyFrame {
  private:
   std::vector<MapPoint*> mvpMapPoints;
   cv::Mat Tcw;
+  std::vector<KeyFrame*> mvpOrderedConnectedKeyFrames;
+  bool mbBad = false;
 };
 
 }  // namespace ORB_SLAM2

@@ -80,6 +80,43 @@ int ORBmatcher::SearchByProjection(Frame& F, const std::vector<MapPoint*>& vp, c
   return n;
 }
 
+int ORBmatcher::SearchByProjection(Frame& Cur, KeyFrame* pKF,
+                                   const std::set<MapPoint*>& sAlreadyFound, const float th,
+                                   const int ORBdist) {
+  const std::vector<MapPoint*> vpMPs = pKF->GetMapPointMatches();
+  const int N = Cur.N, M = (int)vpMPs.size();
+  const size_t M1 = M > 0 ? M : 1;
+  std::vector<uint8_t> held(N > 0 ? N : 1, 0), valid(M1, 0), found(M1, 0);
+  std::vector<float> angle(M1, 0.f), xyz(3 * M1, 0.f), dmin(M1, 0.f), dmax(M1, 0.f);
+  std::vector<int32_t> match(N > 0 ? N : 1, -1);
+  cv::Mat desc((int)M1, 32, cv::CV_8U);
+  for (int i = 0; i < N; i++) held[i] = Cur.mvpMapPoints[i] != nullptr;
+  for (int j = 0; j < M; j++) {
+    MapPoint* p = vpMPs[j];
+    angle[j] = pKF->mvKeysUn[j].angle;
+    if (!p) continue;
+    valid[j] = !p->isBad();   // ORBmatcher.cc:1913-1916
+    found[j] = sAlreadyFound.count(p) != 0;
+    cv::Mat X = p->GetWorldPos();
+    for (int k = 0; k < 3; k++) xyz[3 * j + k] = X.at<float>(k, 0);
+    dmin[j] = p->GetMinDistance();
+    dmax[j] = p->GetMaxDistance();
+    std::memcpy(desc.ptr<uint8_t>(j), p->GetDescriptor().data, 32);
+  }
+  const orbpl_camera cam = Cur.Camera();
+  const orbpl_match_current c{N, Cur.mTcw.ptr<float>(),
+                              reinterpret_cast<const orbpl_keypoint*>(Cur.mvKeysUn.data()),
+                              Cur.mDescriptors.data, Cur.mvuRight.data()};
+  int n = 0;
+  check(orbm_search_by_projection_kf(&cam, Cur.mvScaleFactors.data(), Cur.mnScaleLevels, &c,
+                                     held.data(), M, angle.data(), valid.data(), found.data(),
+                                     xyz.data(), dmin.data(), dmax.data(), desc.data, th, ORBdist,
+                                     mbCheckOrientation ? 1 : 0, match.data(), &n));
+  for (int i = 0; i < N; i++)
+    if (match[i] >= 0) Cur.mvpMapPoints[i] = vpMPs[match[i]];
+  return n;
+}
+
 // the FeatureVector as one node id per feature (-1: none)
 static std::vector<int32_t> nodes_of(const DBoW2::FeatureVector& fv, int n) {
   std::vector<int32_t> node(n > 0 ? n : 1, -1);

@@ -1,6 +1,8 @@
 // Drop-in ORB_SLAM2::ORBmatcher, the tracking overloads (include/ORBmatcher.h:
-// 49-140, src/ORBmatcher.cc:72-183, 247-410, 1710-1879, 2083-2103) over orbm_*.
+// 49-140, src/ORBmatcher.cc:72-183, 247-410, 1710-1879, 1891-2024, 2083-2103)
+// over orbm_*.
 #pragma once
+#include <set>
 #include <vector>
 
 #include "Frame.h"
@@ -28,6 +30,13 @@ class ORBmatcher {
   // frame's FeatureVectors (ComputeBoW first), ORBmatcher.h:140,
   // ORBmatcher.cc:247-410
   int SearchByBoW(KeyFrame* pKF, Frame& F, std::vector<MapPoint*>& vpMapPointMatches);
+
+  // Tracking::Relocalization (Tracking.cc:2201, 2215): the keyframe's map
+  // points that are not in sAlreadyFound projected with CurrentFrame.mTcw
+  // (ORBmatcher.h:108, ORBmatcher.cc:1891-2024)
+  int SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF,
+                         const std::set<MapPoint*>& sAlreadyFound, const float th,
+                         const int ORBdist);
 
   float mfNNratio;
   bool mbCheckOrientation;

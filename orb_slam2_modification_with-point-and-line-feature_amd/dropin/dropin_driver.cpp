@@ -31,6 +31,10 @@
 //   0's pose, SearchByProjection(F2, frame 0's map lines with IsInFrustum,
 //   new_kls, match_indices) and SearchByProjection(F2, KF0, vpMapLineMatches);
 //   formats at harness_mode()
+//   dropin_driver --reloc <in.bin> <out.bin>: Tracking::Relocalization's two
+//   deterministic calls on a dumped case: ORBmatcher(0.75, checkOri).
+//   SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) and
+//   KeyFrameDatabase::DetectRelocalizationCandidates(&F); formats at reloc_mode()
 //   dropin_driver --fail: a Frame from an 8x8 image, which the library's
 //   extractors reject: the error must reach the caller as an exception (the
 //   line thread joined first), printed as "caught: <message>", exit 0
@@ -61,11 +65,13 @@
 #include <cstdio>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <vector>
 
 #include "Frame.h"
 #include "KeyFrame.h"
+#include "KeyFrameDatabase.h"
 #include "LineMatcher.h"
 #include "ORBmatcher.h"
 #include "Optimizer.h"
@@ -356,6 +362,155 @@ static int harness_mode(const char* inp, const char* outp) {
   return 0;
 }
 
+// --reloc in.bin out.bin: the two relocalisation calls on a dumped case
+// through the drop-in classes (Tracking::Relocalization's
+// KeyFrameDatabase::DetectRelocalizationCandidates and ORBmatcher::
+// SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)).
+// in.bin : int32 W, H; float fx fy cx cy k1 k2 p1 p2 k3 bf mThDepth;
+//          int32 nlevels; float scale[nlevels];
+//          matcher: float Tcw[16]; int32 N; keysUn (N x 28 B); desc (N x 32);
+//          u8 held[N]; int32 M; float angle[M]; u8 valid[M], found[M]; float
+//          xyz[3M], minDist[M], maxDist[M]; u8 mpDesc[32M]; float th; int32
+//          ORBdist, checkOri;
+//          database: int32 K; int32 off[K + 1]; u32 words[off[K]]; f64
+//          vals[off[K]]; int32 covis[10K] (-1 none); float relocScore[K];
+//          int32 Q; u32 qwords[Q]; f64 qvals[Q]
+// out.bin: int32 nmatches; int32 match[N] (keyframe feature or -1); int32
+//          ncand; int32 cand[ncand]; int32 mnRelocWords[K] (0: mnRelocQuery
+//          not set); float mRelocScore[K]
+static int reloc_mode(const char* inp, const char* outp) {
+  FILE* in = fopen(inp, "rb");
+  if (!in) throw std::runtime_error("cannot open input");
+  int32_t wh[2], nlev;
+  float camv[11];
+  rd(in, wh, 2);
+  rd(in, camv, 11);
+  rd(in, &nlev, 1);
+  std::vector<float> scale(nlev);
+  rd(in, scale.data(), nlev);
+  Frame F;
+  Frame::fx = camv[0]; Frame::fy = camv[1]; Frame::cx = camv[2]; Frame::cy = camv[3];
+  F.mDistCoef.create(1, 5, cv::CV_32F);
+  for (int k = 0; k < 5; k++) F.mDistCoef.at<float>(0, k) = camv[4 + k];
+  F.mbf = camv[9];
+  F.mThDepth = camv[10];
+  F.mnWidth = wh[0];
+  F.mnHeight = wh[1];
+  F.mnScaleLevels = nlev;
+  F.mvScaleFactors = scale;
+  F.mTcw.create(4, 4, cv::CV_32F);
+  rd(in, F.mTcw.ptr<float>(), 16);
+  int32_t N, M;
+  rd(in, &N, 1);
+  F.N = N;
+  F.mvKeysUn.resize(N);
+  rd(in, F.mvKeysUn.data(), N);
+  F.mDescriptors.create(N > 0 ? N : 1, 32, cv::CV_8U);
+  rd(in, F.mDescriptors.data, (size_t)N * 32);
+  F.mvuRight.assign(N, -1.0f);
+  std::vector<uint8_t> held(N);
+  rd(in, held.data(), N);
+  const float zero3[3] = {0, 0, 0};
+  const uint8_t zero32[32] = {0};
+  MapPoint heldPoint(zero3, zero32);
+  F.mvpMapPoints.assign(N, nullptr);
+  for (int i = 0; i < N; i++)
+    if (held[i]) F.mvpMapPoints[i] = &heldPoint;
+  rd(in, &M, 1);
+  std::vector<float> angle(M), xyz(3 * (size_t)M), dmin(M), dmax(M);
+  std::vector<uint8_t> valid(M), found(M), mpd(32 * (size_t)M);
+  rd(in, angle.data(), M);
+  rd(in, valid.data(), M);
+  rd(in, found.data(), M);
+  rd(in, xyz.data(), 3 * (size_t)M);
+  rd(in, dmin.data(), M);
+  rd(in, dmax.data(), M);
+  rd(in, mpd.data(), 32 * (size_t)M);
+  float th;
+  int32_t orbDist, checkOri;
+  rd(in, &th, 1);
+  rd(in, &orbDist, 1);
+  rd(in, &checkOri, 1);
+  // the keyframe: a map point per feature; a feature that is not valid has
+  // none (even index) or a bad one (odd index)
+  Frame FK;
+  FK.N = M;
+  FK.mvKeysUn.resize(M);
+  FK.mvpMapPoints.assign(M, nullptr);
+  std::vector<std::unique_ptr<MapPoint>> mps;
+  std::map<const MapPoint*, int> mp_index;
+  std::set<MapPoint*> sFound;
+  for (int j = 0; j < M; j++) {
+    FK.mvKeysUn[j].angle = angle[j];
+    if (!valid[j] && j % 2 == 0) continue;
+    mps.emplace_back(new MapPoint(&xyz[3 * (size_t)j], &mpd[32 * (size_t)j]));
+    mps.back()->SetNormalAndDistances(zero3, dmin[j], dmax[j]);
+    if (!valid[j]) mps.back()->SetBadFlag();
+    if (found[j]) sFound.insert(mps.back().get());
+    FK.mvpMapPoints[j] = mps.back().get();
+    mp_index[mps.back().get()] = j;
+  }
+  KeyFrame KF(FK);
+  ORBmatcher matcher(0.75, checkOri != 0);
+  const int nmatches = matcher.SearchByProjection(F, &KF, sFound, th, orbDist);
+  // the database
+  int32_t K, Q;
+  rd(in, &K, 1);
+  std::vector<int32_t> off(K + 1), covis((size_t)K * 10);
+  rd(in, off.data(), K + 1);
+  std::vector<uint32_t> words(off[K]);
+  std::vector<double> vals(off[K]);
+  std::vector<float> rscore(K);
+  rd(in, words.data(), words.size());
+  rd(in, vals.data(), vals.size());
+  rd(in, covis.data(), covis.size());
+  rd(in, rscore.data(), K);
+  rd(in, &Q, 1);
+  std::vector<uint32_t> qw(Q);
+  std::vector<double> qv(Q);
+  rd(in, qw.data(), Q);
+  rd(in, qv.data(), Q);
+  fclose(in);
+  ORBVocabulary voc;
+  KeyFrameDatabase db(voc);
+  std::vector<std::unique_ptr<KeyFrame>> kfs;
+  std::map<const KeyFrame*, int> kf_index;
+  for (int k = 0; k < K; k++) {
+    Frame B;
+    for (int e = off[k]; e < off[k + 1]; e++) B.mBowVec[words[e]] = vals[e];
+    kfs.emplace_back(new KeyFrame(B));
+    kfs.back()->mRelocScore = rscore[k];
+    kf_index[kfs.back().get()] = k;
+  }
+  for (int k = 0; k < K; k++) {
+    std::vector<KeyFrame*> ordered;
+    for (int c = 0; c < 10; c++) {
+      const int j = covis[(size_t)k * 10 + c];
+      if (j >= 0) ordered.push_back(kfs[j].get());
+    }
+    kfs[k]->SetOrderedCovisibles(ordered);
+    db.add(kfs[k].get());
+  }
+  F.mnId = 12345;
+  for (int e = 0; e < Q; e++) F.mBowVec[qw[e]] = qv[e];
+  const std::vector<KeyFrame*> cands = db.DetectRelocalizationCandidates(&F);
+  FILE* o = fopen(outp, "wb");
+  if (!o) throw std::runtime_error("cannot open output");
+  wr1<int32_t>(o, nmatches);
+  for (int i = 0; i < N; i++) {
+    const MapPoint* p = F.mvpMapPoints[i];
+    wr1<int32_t>(o, (p && p != &heldPoint) ? mp_index.at(p) : -1);
+  }
+  wr1<int32_t>(o, (int32_t)cands.size());
+  for (KeyFrame* c : cands) wr1<int32_t>(o, kf_index.at(c));
+  for (int k = 0; k < K; k++)
+    wr1<int32_t>(o, kfs[k]->mnRelocQuery == F.mnId ? kfs[k]->mnRelocWords : 0);
+  for (int k = 0; k < K; k++) wr1<float>(o, kfs[k]->mRelocScore);
+  fclose(o);
+  printf("dropin_driver --reloc: %d matches, %d candidates\n", nmatches, (int)cands.size());
+  return 0;
+}
+
 static int fail_mode() {
   ORBextractor ex(1000, 1.2f, 8, 20, 7);
   cv::Mat K = cv::Mat::eye(3, 3, cv::CV_32F);
@@ -388,6 +543,14 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  if (argc == 4 && std::string(argv[1]) == "--reloc") {
+    try {
+      return reloc_mode(argv[2], argv[3]);
+    } catch (const std::exception& e) {
+      fprintf(stderr, "dropin_driver: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc == 4 && std::string(argv[1]) == "--stereo") {
     try {
       return stereo_mode(argv[2], argv[3]);
@@ -398,7 +561,8 @@ int main(int argc, char** argv) {
   }
   const bool timing = argc == 4 && std::string(argv[1]) == "--time";
   if (argc != 3 && !timing) {
-    fprintf(stderr, "usage: dropin_driver in.bin out.bin | dropin_driver --time in.bin K\n");
+    fprintf(stderr, "usage: dropin_driver in.bin out.bin | dropin_driver --time in.bin K | "
+                    "dropin_driver --reloc in.bin out.bin\n");
     return 2;
   }
   try {
