@@ -348,9 +348,9 @@ int orbm_search_by_bow(int nkf, const int32_t* kf_node, const uint8_t* kf_valid,
 
 /* ------------------------------------------------------------------------
  * Tracking::Relocalization (Tracking.cc:2049-2269): its place recognition and
- * its projection matcher. With orbv_transform (Frame::ComputeBoW),
- * orbm_search_by_bow and orbpl_pose_optimization the function lacks only
- * PnPsolver.
+ * its projection matcher and its PnP solver. With orbv_transform
+ * (Frame::ComputeBoW), orbm_search_by_bow and orbpl_pose_optimization these
+ * are all the building blocks of the function.
  * ---------------------------------------------------------------------- */
 #define ORBKF_MAX_KEYFRAMES 64   /* keyframes per database (ORBPL_MAP_KF's maximum) */
 #define ORBKF_MAX_WORDS 4096     /* BowVector entries per vector (orbv_transform's cap) */
@@ -463,6 +463,91 @@ int orbm_search_by_projection_kf_batch_device(const orbpl_camera* cam, const flo
                                               int nlevels, const orbm_kf_device_batch* b,
                                               int batch, float th, int orb_dist, int check_ori,
                                               void* stream);
+
+/* PnPsolver (PnPsolver.cc): EPnP inside RANSAC, one
+ * solver per (lost frame, candidate keyframe), any number of solvers in one
+ * launch. */
+#define ORBPNP_MAX_POINTS 2048      /* correspondences per solver */
+#define ORBPNP_MAX_ITERATIONS 320   /* hypotheses one call may run per solver */
+#define ORBPNP_MIN_SET 4            /* mRansacMinSet; no other value is built */
+/* PnPsolver::SetRansacParameters (:121-157) for n correspondences, on the
+ * host, no device needed: the adjusted mRansacMinInliers, mRansacMaxIts and
+ * mRansacEpsilon, and, if max_error is not NULL, mvMaxError[i] = sigma2[i] *
+ * th2 (n entries each). log / pow are the platform's. A quotient that is not
+ * a finite int (n == 0, epsilon^3 below 2^-53) counts as INT_MIN, so max_its
+ * is 1. */
+int orbpnp_ransac_parameters(int n, double probability, int min_inliers, int max_iterations,
+                             int min_set, float epsilon, float th2, const float* sigma2,
+                             int32_t* out_min_inliers, int32_t* out_max_its, float* out_epsilon,
+                             float* max_error);
+/* One solver. Inputs: the camera, the n correspondences (p2d[n][2] =
+ * mvP2D, sigma2[n] = mvSigma2 (not read, may be NULL), p3d[n][3] = mvP3Dw),
+ * the adjusted RANSAC parameters (min_inliers >= 4, max_its, max_error[n]) and
+ * n_draws raw rand() values in [0, RAND_MAX]: hypothesis k of a call uses
+ * draws[4k .. 4k+3], a call may run max(max_its - *iterations, n_iterations)
+ * hypotheses and n_draws must cover them. State, in/out, zero before the first
+ * call: *iterations = mnIterations, *best_inliers = mnBestInliers,
+ * best_mask[n] = mvbBestInliers, best_Tcw[16] = mBestTcw. Outputs: Tcw[16]
+ * (row-major; all zero when *result == 0), *result (0 = empty cv::Mat, 1 =
+ * the refined pose, 2 = mBestTcw at exhaustion), *no_more = bNoMore,
+ * *n_inliers, inliers[n] per correspondence, *draws_consumed = 4 x the
+ * hypotheses the reference would have run before it returned. */
+typedef struct orbpnp_problem {
+  float fx, fy, cx, cy;
+  int32_t n;
+  const float* p2d;
+  const float* sigma2;
+  const float* p3d;
+  int32_t min_inliers;
+  int32_t max_its;
+  const float* max_error;
+  int32_t n_draws;
+  const int32_t* draws;
+  int32_t* iterations;
+  int32_t* best_inliers;
+  uint8_t* best_mask;
+  float* best_Tcw;
+  float* Tcw;
+  int32_t* result;
+  int32_t* no_more;
+  int32_t* n_inliers;
+  uint8_t* inliers;
+  int32_t* draws_consumed;
+} orbpnp_problem;
+/* PnPsolver::iterate(n_iterations, ...) for nsolvers independent solvers in
+ * one launch. ORBPL_ERR_ARG: n above ORBPNP_MAX_POINTS, min_inliers below 4, a
+ * call that may run more than ORBPNP_MAX_ITERATIONS hypotheses, or too few
+ * draws. */
+int orbpnp_iterate(const orbpnp_problem* problems, int nsolvers, int n_iterations);
+/* The same over pitched device arrays, asynchronous on `stream`: solver s's
+ * correspondences, masks and max_error start at s * pt_pitch entries, its
+ * draws at s * draw_pitch, its camera at d_cam + 4 s (fx fy cx cy), its poses
+ * at 16 s. Counts above the caps are clamped, the hypotheses of a call also to
+ * draw_pitch / 4. */
+typedef struct orbpnp_device_batch {
+  const int32_t* d_n;
+  const float* d_cam;
+  const float* d_p2d;
+  const float* d_p3d;
+  const float* d_max_error;
+  int32_t pt_pitch;
+  const int32_t* d_min_inliers;
+  const int32_t* d_max_its;
+  const int32_t* d_draws;
+  int32_t draw_pitch;
+  int32_t* d_iterations;
+  int32_t* d_best_inliers;
+  uint8_t* d_best_mask;
+  float* d_best_Tcw;
+  float* d_Tcw;
+  int32_t* d_result;
+  int32_t* d_no_more;
+  int32_t* d_n_inliers;
+  uint8_t* d_inliers;
+  int32_t* d_draws_consumed;
+} orbpnp_device_batch;
+int orbpnp_iterate_batch_device(const orbpnp_device_batch* b, int nsolvers, int n_iterations,
+                                void* stream);
 
 /* ------------------------------------------------------------------------
  * Optimizer::PoseOptimization / PoseOptimizationWithLines

@@ -452,6 +452,10 @@ def _declare_track(L):
     L.orbm_search_by_projection_kf_batch_device.argtypes = [vp, vp, i, vp, i, C.c_float, i, i, vp]
     L.orbkf_detect_reloc.argtypes = [vp, i, i]
     L.orbkf_detect_reloc_batch_device.argtypes = [vp, i, i, vp]
+    L.orbpnp_ransac_parameters.argtypes = [i, C.c_double, i, i, i, C.c_float, C.c_float, vp, vp,
+                                           vp, vp, vp]
+    L.orbpnp_iterate.argtypes = [vp, i, i]
+    L.orbpnp_iterate_batch_device.argtypes = [vp, i, i, vp]
 
 
 _declare_orig = _declare
@@ -1450,3 +1454,285 @@ class KeyFrameDatabase:
             self._score[k] = out["reloc_score"][j]
         self.last_common_words = {k: int(out["common_words"][j]) for j, k in enumerate(live)}
         return [live[j] for j in out["cand"]]
+
+
+# ---------------------------------------------------------------------------
+# PnPsolver (PnPsolver.cc)
+# ---------------------------------------------------------------------------
+PNP_MAX_POINTS = 2048
+PNP_MAX_ITERATIONS = 320
+PNP_RAND_MAX = 2147483647
+
+
+class PnpProblem(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("n", C.c_int32), ("p2d", C.c_void_p), ("sigma2", C.c_void_p),
+                ("p3d", C.c_void_p), ("min_inliers", C.c_int32), ("max_its", C.c_int32),
+                ("max_error", C.c_void_p), ("n_draws", C.c_int32), ("draws", C.c_void_p),
+                ("iterations", C.c_void_p), ("best_inliers", C.c_void_p),
+                ("best_mask", C.c_void_p), ("best_Tcw", C.c_void_p), ("Tcw", C.c_void_p),
+                ("result", C.c_void_p), ("no_more", C.c_void_p), ("n_inliers", C.c_void_p),
+                ("inliers", C.c_void_p), ("draws_consumed", C.c_void_p)]
+
+
+class PnpDeviceBatch(C.Structure):
+    _fields_ = [("d_n", C.c_void_p), ("d_cam", C.c_void_p), ("d_p2d", C.c_void_p),
+                ("d_p3d", C.c_void_p), ("d_max_error", C.c_void_p), ("pt_pitch", C.c_int32),
+                ("d_min_inliers", C.c_void_p), ("d_max_its", C.c_void_p),
+                ("d_draws", C.c_void_p), ("draw_pitch", C.c_int32),
+                ("d_iterations", C.c_void_p), ("d_best_inliers", C.c_void_p),
+                ("d_best_mask", C.c_void_p), ("d_best_Tcw", C.c_void_p), ("d_Tcw", C.c_void_p),
+                ("d_result", C.c_void_p), ("d_no_more", C.c_void_p),
+                ("d_n_inliers", C.c_void_p), ("d_inliers", C.c_void_p),
+                ("d_draws_consumed", C.c_void_p)]
+
+
+def pnp_ransac_parameters(N, probability=0.99, minInliers=8, maxIterations=300, minSet=4,
+                          epsilon=0.4, th2=5.991, sigma2=None):
+    """PnPsolver::SetRansacParameters (:121-157) on the host, with the
+    platform's log / pow. Returns (min_inliers, max_its, epsilon, max_error):
+    the adjusted parameters and mvMaxError (None without sigma2)."""
+    import math
+    f32 = np.float32
+    eps = f32(epsilon)
+    with np.errstate(all="ignore"):
+        n_min = int(f32(N) * eps)
+        if n_min < minInliers:
+            n_min = minInliers
+        if n_min < minSet:
+            n_min = minSet
+        ratio = f32(n_min) / f32(N)
+        if eps < ratio:
+            eps = ratio
+    if n_min == N:
+        n_it = 1
+    else:
+        try:
+            v = math.ceil(math.log(1 - probability) / math.log(1 - math.pow(float(eps), 3)))
+        except (ValueError, ZeroDivisionError, OverflowError):
+            v = None      # not a finite int: INT_MIN, as the C library pins it
+        n_it = v if (v is not None and -2 ** 31 <= v < 2 ** 31) else -2 ** 31
+    max_its = max(1, min(n_it, maxIterations))
+    max_error = None
+    if sigma2 is not None:
+        max_error = _c(sigma2, f32) * f32(th2)
+    return n_min, max_its, f32(eps), max_error
+
+
+def pnp_hypotheses(n, min_inliers, max_its, iterations, n_iterations):
+    """hypotheses iterate(n_iterations) runs at most from this state: a call
+    needs 4 draws for each"""
+    if n < min_inliers:
+        return 0
+    return max(0, max_its - iterations, n_iterations)
+
+
+def pnp_new_state(n):
+    return dict(iterations=0, best_inliers=0, best_mask=np.zeros(n, np.uint8),
+                best_Tcw=np.zeros((4, 4), np.float32))
+
+
+def pnp_iterate_batch(problems, n_iterations):
+    """PnPsolver::iterate(n_iterations) for a list of independent solvers in
+    one launch. Each problem is a dict: ``cam`` = (fx, fy, cx, cy), ``p2d``
+    [n, 2], ``p3d`` [n, 3], ``max_error`` [n] (float32), ``min_inliers``,
+    ``max_its`` (adjusted, see pnp_ransac_parameters), ``draws`` = raw rand()
+    values, 4 per hypothesis the call may run (pnp_hypotheses), ``state`` =
+    the dict the previous call returned (missing or None: a new solver).
+    Returns per problem a dict: ``result`` (0 empty, 1 refined, 2 best at
+    exhaustion), ``no_more``, ``n_inliers``, ``inliers`` bool[n], ``Tcw``
+    float32[4, 4], ``draws_consumed``, ``state``."""
+    ns = len(problems)
+    arr = (PnpProblem * max(1, ns))()
+    keep, outs = [], []
+    f32, i32 = np.float32, np.int32
+    for p, pr in enumerate(problems):
+        p2 = _c(pr["p2d"], f32).reshape(-1, 2)
+        p3 = _c(pr["p3d"], f32).reshape(-1, 3)
+        n = len(p2)
+        me = _c(pr["max_error"], f32).reshape(-1)
+        if len(p3) != n or len(me) != n:
+            raise OrbplError("p2d, p3d and max_error differ in length")
+        dr = _c(pr["draws"], i32).reshape(-1)
+        st = pr.get("state") or pnp_new_state(n)
+        it = np.array([st["iterations"]], i32)
+        bi = np.array([st["best_inliers"]], i32)
+        bm = _c(st["best_mask"], np.uint8).copy()
+        bT = _c(st["best_Tcw"], f32).reshape(16).copy()
+        if len(bm) != n:
+            raise OrbplError("state belongs to another problem")
+        T = np.zeros(16, f32)
+        res, nm, ni, dc = (np.zeros(1, i32) for _ in range(4))
+        inl = np.zeros(max(1, n), np.uint8)
+        cam = [float(c) for c in pr["cam"]]
+        keep += [p2, p3, me, dr, it, bi, bm, bT, T, res, nm, ni, dc, inl]
+        arr[p] = PnpProblem(cam[0], cam[1], cam[2], cam[3], n, _ptr(p2), None, _ptr(p3),
+                            int(pr["min_inliers"]), int(pr["max_its"]), _ptr(me), len(dr),
+                            _ptr(dr), _ptr(it), _ptr(bi), _ptr(bm), _ptr(bT), _ptr(T), _ptr(res),
+                            _ptr(nm), _ptr(ni), _ptr(inl), _ptr(dc))
+        outs.append((n, it, bi, bm, bT, T, res, nm, ni, dc, inl))
+    check(lib().orbpnp_iterate(C.byref(arr), ns, int(n_iterations)), "orbpnp_iterate")
+    return [dict(result=int(res[0]), no_more=bool(nm[0]), n_inliers=int(ni[0]),
+                 inliers=inl[:n].astype(bool), Tcw=T.reshape(4, 4).copy(),
+                 draws_consumed=int(dc[0]),
+                 state=dict(iterations=int(it[0]), best_inliers=int(bi[0]), best_mask=bm,
+                            best_Tcw=bT.reshape(4, 4)))
+            for n, it, bi, bm, bT, T, res, nm, ni, dc, inl in outs]
+
+
+# rand() is process-wide in the reference; so is the look-ahead queue (P29): a
+# call is handed 4 draws per hypothesis it may run, the ones it did not consume
+# stay queued and go to the next call, of whichever solver.
+_pnp_rand_queue = []
+_libc = None
+
+
+def _pnp_libc():
+    global _libc
+    if _libc is None:
+        _libc = C.CDLL(None)
+        _libc.rand.restype = C.c_int
+    return _libc
+
+
+def pnp_srand(seed):
+    """srand(seed) of the C library, dropping the draws queued before it"""
+    _pnp_libc().srand(C.c_uint(seed))
+    del _pnp_rand_queue[:]
+
+
+def _pnp_take_rand(count):
+    _pnp_libc()
+    while len(_pnp_rand_queue) < count:
+        _pnp_rand_queue.append(_libc.rand())
+    return np.array(_pnp_rand_queue[:count], np.int32)
+
+
+class PnPsolver:
+    """ORB_SLAM2::PnPsolver(F, vpMapPointMatches) (:67-110): ``cam`` = (fx, fy,
+    cx, cy) or a camera with those fields, ``kps_un_xy`` [n, 2] = F.mvKeysUn's
+    points, ``level_sigma2_per_keypoint`` [n] = F.mvLevelSigma2[kp.octave],
+    ``mp_xyz`` [n, 3] = the matched map points' world positions, ``mp_valid``
+    [n] = the match exists and is not bad. The correspondences are the valid
+    keypoints in index order (mvKeyPointIndices)."""
+
+    def __init__(self, cam, kps_un_xy, level_sigma2_per_keypoint, mp_xyz, mp_valid):
+        if hasattr(cam, "fx"):
+            cam = (cam.fx, cam.fy, cam.cx, cam.cy)
+        self.cam = tuple(float(np.float32(c)) for c in cam)
+        valid = np.asarray(mp_valid).astype(bool).reshape(-1)
+        self.n_keypoints = len(valid)
+        self.mvKeyPointIndices = np.flatnonzero(valid)
+        self.p2d = _c(np.asarray(kps_un_xy, np.float32).reshape(-1, 2)[valid], np.float32)
+        self.sigma2 = _c(np.asarray(level_sigma2_per_keypoint, np.float32).reshape(-1)[valid],
+                         np.float32)
+        self.p3d = _c(np.asarray(mp_xyz, np.float32).reshape(-1, 3)[valid], np.float32)
+        self.N = len(self.p2d)
+        if self.N > PNP_MAX_POINTS:
+            raise OrbplError(f"more than {PNP_MAX_POINTS} correspondences")
+        self.state = pnp_new_state(self.N)
+        self.SetRansacParameters()
+
+    def SetRansacParameters(self, probability=0.99, minInliers=8, maxIterations=300, minSet=4,
+                            epsilon=0.4, th2=5.991):
+        if minSet != 4:
+            raise OrbplError("only minSet = 4 is built")
+        self.min_inliers, self.max_its, self.epsilon, self.max_error = pnp_ransac_parameters(
+            self.N, probability, minInliers, maxIterations, minSet, epsilon, th2, self.sigma2)
+
+    def iterate(self, nIterations, draws=None):
+        """Returns (Tcw float32[4, 4] or None, bNoMore, vbInliers bool per
+        keypoint, nInliers). ``draws`` = raw rand() values for this call (4 per
+        hypothesis it may run); None takes them from the C library's rand()
+        through the process-wide look-ahead queue."""
+        need = 4 * pnp_hypotheses(self.N, self.min_inliers, self.max_its,
+                                  self.state["iterations"], nIterations)
+        own = draws is None
+        d = _pnp_take_rand(need) if own else _c(draws, np.int32)
+        o = pnp_iterate_batch([dict(cam=self.cam, p2d=self.p2d, p3d=self.p3d,
+                                    max_error=self.max_error, min_inliers=self.min_inliers,
+                                    max_its=self.max_its, draws=d, state=self.state)],
+                              nIterations)[0]
+        if own:
+            del _pnp_rand_queue[:o["draws_consumed"]]
+        self.state = o["state"]
+        self.last = o
+        vb = np.zeros(self.n_keypoints, bool)
+        if o["result"]:
+            vb[self.mvKeyPointIndices[o["inliers"]]] = True
+        return (o["Tcw"] if o["result"] else None), o["no_more"], vb, o["n_inliers"]
+
+    def find(self):
+        """(Tcw or None, vbInliers, nInliers)"""
+        T, _, vb, n = self.iterate(self.max_its)
+        return T, vb, n
+
+
+class PnpDeviceProblems:
+    """The pitched device arrays of orbpnp_iterate_batch_device for a list of
+    problems (dicts as for pnp_iterate_batch): iterate() launches on the null
+    stream without a host round trip, download() synchronises and returns the
+    outputs and the state as pnp_iterate_batch does."""
+
+    def __init__(self, problems, draw_pitch=4 * PNP_MAX_ITERATIONS, device=0):
+        f32, i32, u8 = np.float32, np.int32, np.uint8
+        self.ns = ns = len(problems)
+        self.n = np.array([len(_c(p["p2d"], f32).reshape(-1, 2)) for p in problems], i32)
+        self.pt_pitch = ptp = max(1, int(self.n.max()) if ns else 1)
+        self.draw_pitch = int(draw_pitch)
+        S = max(1, ns)
+        cam = np.zeros((S, 4), f32)
+        p2, p3 = np.zeros((S, ptp, 2), f32), np.zeros((S, ptp, 3), f32)
+        me, dr = np.zeros((S, ptp), f32), np.zeros((S, self.draw_pitch), i32)
+        mn, mx, it, bi = (np.zeros(S, i32) for _ in range(4))
+        bm, bT = np.zeros((S, ptp), u8), np.zeros((S, 16), f32)
+        for s, p in enumerate(problems):
+            n = self.n[s]
+            cam[s] = [float(c) for c in p["cam"]]
+            p2[s, :n] = _c(p["p2d"], f32).reshape(-1, 2)
+            p3[s, :n] = _c(p["p3d"], f32).reshape(-1, 3)
+            me[s, :n] = _c(p["max_error"], f32).reshape(-1)
+            d = _c(p["draws"], i32).reshape(-1)[:self.draw_pitch]
+            dr[s, :len(d)] = d
+            mn[s], mx[s] = p["min_inliers"], p["max_its"]
+            st = p.get("state") or pnp_new_state(n)
+            it[s], bi[s] = st["iterations"], st["best_inliers"]
+            bm[s, :n] = st["best_mask"]
+            bT[s] = _c(st["best_Tcw"], f32).reshape(16)
+        mk = lambda a: DeviceBuffer.from_array(a, device)
+        self.bufs = dict(n=mk(self.n if ns else np.zeros(1, i32)), cam=mk(cam), p2d=mk(p2),
+                         p3d=mk(p3), max_error=mk(me), min_inliers=mk(mn), max_its=mk(mx),
+                         draws=mk(dr), iterations=mk(it), best_inliers=mk(bi), best_mask=mk(bm),
+                         best_Tcw=mk(bT), Tcw=mk(np.zeros((S, 16), f32)),
+                         result=mk(np.zeros(S, i32)), no_more=mk(np.zeros(S, i32)),
+                         n_inliers=mk(np.zeros(S, i32)), inliers=mk(np.zeros((S, ptp), u8)),
+                         draws_consumed=mk(np.zeros(S, i32)))
+        b = self.bufs
+        self.batch = PnpDeviceBatch(b["n"].ptr, b["cam"].ptr, b["p2d"].ptr, b["p3d"].ptr,
+                                    b["max_error"].ptr, ptp, b["min_inliers"].ptr,
+                                    b["max_its"].ptr, b["draws"].ptr, self.draw_pitch,
+                                    b["iterations"].ptr, b["best_inliers"].ptr,
+                                    b["best_mask"].ptr, b["best_Tcw"].ptr, b["Tcw"].ptr,
+                                    b["result"].ptr, b["no_more"].ptr, b["n_inliers"].ptr,
+                                    b["inliers"].ptr, b["draws_consumed"].ptr)
+        self.device = device
+
+    def iterate(self, n_iterations, stream=None):
+        check(lib().orbpnp_iterate_batch_device(C.byref(self.batch), self.ns, int(n_iterations),
+                                                stream), "orbpnp_iterate_batch_device")
+
+    def download(self):
+        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
+        S, ptp, b = max(1, self.ns), self.pt_pitch, self.bufs
+        i32 = np.int32
+        res, nm = b["result"].download(i32, S), b["no_more"].download(i32, S)
+        ni, dc = b["n_inliers"].download(i32, S), b["draws_consumed"].download(i32, S)
+        it, bi = b["iterations"].download(i32, S), b["best_inliers"].download(i32, S)
+        inl, bm = (b[k].download(np.uint8, (S, ptp)) for k in ("inliers", "best_mask"))
+        T, bT = (b[k].download(np.float32, (S, 4, 4)) for k in ("Tcw", "best_Tcw"))
+        return [dict(result=int(res[s]), no_more=bool(nm[s]), n_inliers=int(ni[s]),
+                     inliers=inl[s, :self.n[s]].astype(bool), Tcw=T[s].copy(),
+                     draws_consumed=int(dc[s]),
+                     state=dict(iterations=int(it[s]), best_inliers=int(bi[s]),
+                                best_mask=bm[s, :self.n[s]].copy(), best_Tcw=bT[s].copy()))
+                for s in range(self.ns)]

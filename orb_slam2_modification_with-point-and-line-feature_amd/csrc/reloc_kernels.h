@@ -1,5 +1,6 @@
-// Device launchers of the two deterministic pieces of Tracking::Relocalization
-// (Tracking.cc:2049-2269) that are not shared with the tracking step:
+// Device launchers of the pieces of Tracking::Relocalization
+// (Tracking.cc:2049-2269) that are not shared with the tracking step
+// (launch_pnp_iterate, the PnP solver, is declared at the end):
 //   launch_kfdb_reloc : KeyFrameDatabase::DetectRelocalizationCandidates
 //                       (KeyFrameDatabase.cc:274-412), kfdb.hip
 //   launch_match_kf   : ORBmatcher::SearchByProjection(Frame&, KeyFrame*,
@@ -67,5 +68,38 @@ struct MatchKfArgs {
   float log_scale;               // Frame::mfLogScaleFactor (P15)
 };
 void launch_match_kf(const TrackConsts& c, const MatchKfArgs& a, int batch, hipStream_t s);
+
+//   launch_pnp_iterate : PnPsolver::iterate (PnPsolver.cc:165-258), pnp.hip
+constexpr int kPnpMaxPoints = 2048;  // correspondences per solver (ORBPNP_MAX_POINTS)
+constexpr int kPnpMaxIts = 320;      // hypotheses per call (ORBPNP_MAX_ITERATIONS)
+
+// Solver s = blockIdx.x; its correspondences at s * pt_pitch, its draws at
+// s * draw_pitch. n is clamped to kPnpMaxPoints, the hypotheses of the call to
+// min(kPnpMaxIts, draw_pitch / 4).
+struct PnpArgs {
+  const int* n;                // [ns] correspondences
+  const float* cam;            // [ns][4] fx fy cx cy
+  const float* p2d;            // [pt_pitch][2] per solver
+  const float* p3d;            // [pt_pitch][3]
+  const float* max_error;      // mvMaxError
+  int pt_pitch;
+  const int* min_inliers;      // mRansacMinInliers, adjusted
+  const int* max_its;          // mRansacMaxIts, adjusted
+  const int* draws;            // raw rand() values, 4 per hypothesis (P29)
+  int draw_pitch;
+  double rand_max_p1;          // (double)RAND_MAX + 1.0
+  int n_iterations;            // iterate()'s argument
+  int* iterations;             // mnIterations, in/out
+  int* best_count;             // mnBestInliers, in/out
+  uint8_t* best_mask;          // mvbBestInliers, in/out, pt_pitch per solver
+  float* best_Tcw;             // mBestTcw, in/out, 16 per solver
+  float* Tcw;                  // 16 per solver; zero when result == 0
+  int* result;                 // 0 empty, 1 refined, 2 best at exhaustion
+  int* no_more;
+  int* n_inliers;
+  uint8_t* inliers;            // pt_pitch per solver
+  int* draws_consumed;
+};
+void launch_pnp_iterate(const PnpArgs& a, int nsolvers, hipStream_t s);
 
 }  // namespace orbpl

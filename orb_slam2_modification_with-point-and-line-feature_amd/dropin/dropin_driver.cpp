@@ -35,6 +35,8 @@
 //   deterministic calls on a dumped case: ORBmatcher(0.75, checkOri).
 //   SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) and
 //   KeyFrameDatabase::DetectRelocalizationCandidates(&F); formats at reloc_mode()
+//   dropin_driver --pnp <in.bin> <out.bin>: one ORB_SLAM2::PnPsolver on a dumped
+//   problem, iterate(n) repeated until a pose or bNoMore; formats at pnp_mode()
 //   dropin_driver --fail: a Frame from an 8x8 image, which the library's
 //   extractors reject: the error must reach the caller as an exception (the
 //   line thread joined first), printed as "caught: <message>", exit 0
@@ -75,6 +77,7 @@
 #include "LineMatcher.h"
 #include "ORBmatcher.h"
 #include "Optimizer.h"
+#include "PnPsolver.h"
 
 using namespace ORB_SLAM2;
 
@@ -511,6 +514,85 @@ static int reloc_mode(const char* inp, const char* outp) {
   return 0;
 }
 
+// --pnp in.bin out.bin: Tracking::Relocalization's solver calls (Tracking.cc:
+// 2118-2150) on a dumped problem through the drop-in PnPsolver.
+// in.bin : float fx fy cx cy; int32 nlevels; float levelSigma2[nlevels];
+//          int32 N; float keysUn xy[2N]; int32 octave[N]; u8 point[N] (0: no
+//          map point, 1: a good one, 2: a bad one); float xyz[3N];
+//          double probability; int32 minInliers, maxIterations, minSet; float
+//          epsilon, th2; int32 seed (srand), nIterations
+// out.bin: int32 found (the returned cv::Mat is not empty), bNoMore, nInliers,
+//          calls of iterate(); float Tcw[16] (zero if not found); u8
+//          vbInliers[N] (zero if not found)
+static int pnp_mode(const char* inp, const char* outp) {
+  FILE* in = fopen(inp, "rb");
+  if (!in) throw std::runtime_error("cannot open input");
+  float camv[4];
+  int32_t nlev, N;
+  rd(in, camv, 4);
+  rd(in, &nlev, 1);
+  Frame F;
+  Frame::fx = camv[0]; Frame::fy = camv[1]; Frame::cx = camv[2]; Frame::cy = camv[3];
+  F.mvLevelSigma2.resize(nlev);
+  rd(in, F.mvLevelSigma2.data(), nlev);
+  rd(in, &N, 1);
+  std::vector<float> xy(2 * (size_t)N), xyz(3 * (size_t)N);
+  std::vector<int32_t> octave(N);
+  std::vector<uint8_t> point(N);
+  rd(in, xy.data(), 2 * (size_t)N);
+  rd(in, octave.data(), N);
+  rd(in, point.data(), N);
+  rd(in, xyz.data(), 3 * (size_t)N);
+  double probability;
+  int32_t ip[3], sn[2];
+  float ef[2];
+  rd(in, &probability, 1);
+  rd(in, ip, 3);
+  rd(in, ef, 2);
+  rd(in, sn, 2);
+  fclose(in);
+  F.N = N;
+  F.mvKeysUn.resize(N);
+  const uint8_t zero32[32] = {0};
+  std::vector<std::unique_ptr<MapPoint>> own;
+  std::vector<MapPoint*> vpMapPointMatches(N, nullptr);
+  for (int i = 0; i < N; i++) {
+    F.mvKeysUn[i].pt.x = xy[2 * i];
+    F.mvKeysUn[i].pt.y = xy[2 * i + 1];
+    F.mvKeysUn[i].octave = octave[i];
+    if (!point[i]) continue;
+    own.emplace_back(new MapPoint(&xyz[3 * (size_t)i], zero32));
+    if (point[i] == 2) own.back()->SetBadFlag();
+    vpMapPointMatches[i] = own.back().get();
+  }
+  srand((unsigned)sn[0]);
+  PnPsolver* pSolver = new PnPsolver(F, vpMapPointMatches);
+  pSolver->SetRansacParameters(probability, ip[0], ip[1], ip[2], ef[0], ef[1]);
+  std::vector<bool> vbInliers;
+  int nInliers = 0, calls = 0;
+  bool bNoMore = false;
+  cv::Mat Tcw;
+  do {
+    Tcw = pSolver->iterate(sn[1], bNoMore, vbInliers, nInliers);
+    calls++;
+  } while (Tcw.empty() && !bNoMore);
+  delete pSolver;
+  FILE* o = fopen(outp, "wb");
+  if (!o) throw std::runtime_error("cannot open output");
+  wr1<int32_t>(o, Tcw.empty() ? 0 : 1);
+  wr1<int32_t>(o, bNoMore ? 1 : 0);
+  wr1<int32_t>(o, nInliers);
+  wr1<int32_t>(o, calls);
+  for (int r = 0; r < 4; r++)
+    for (int c = 0; c < 4; c++) wr1<float>(o, Tcw.empty() ? 0.0f : Tcw.at<float>(r, c));
+  for (int i = 0; i < N; i++)
+    wr1<uint8_t>(o, (!Tcw.empty() && i < (int)vbInliers.size() && vbInliers[i]) ? 1 : 0);
+  fclose(o);
+  printf("dropin_driver --pnp: %s, %d inliers, %d calls\n", Tcw.empty() ? "no pose" : "pose",
+         nInliers, calls);
+  return 0;
+}
+
 static int fail_mode() {
   ORBextractor ex(1000, 1.2f, 8, 20, 7);
   cv::Mat K = cv::Mat::eye(3, 3, cv::CV_32F);
@@ -551,6 +633,14 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  if (argc == 4 && std::string(argv[1]) == "--pnp") {
+    try {
+      return pnp_mode(argv[2], argv[3]);
+    } catch (const std::exception& e) {
+      fprintf(stderr, "dropin_driver: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc == 4 && std::string(argv[1]) == "--stereo") {
     try {
       return stereo_mode(argv[2], argv[3]);
@@ -562,7 +652,7 @@ int main(int argc, char** argv) {
   const bool timing = argc == 4 && std::string(argv[1]) == "--time";
   if (argc != 3 && !timing) {
     fprintf(stderr, "usage: dropin_driver in.bin out.bin | dropin_driver --time in.bin K | "
-                    "dropin_driver --reloc in.bin out.bin\n");
+                    "dropin_driver --reloc in.bin out.bin | dropin_driver --pnp in.bin out.bin\n");
     return 2;
   }
   try {
