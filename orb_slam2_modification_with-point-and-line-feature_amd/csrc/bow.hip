@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/orbpl.h"
+#include "block_ops.h"
 #include "orbpl_runtime.h"
 
 namespace orbpl {
@@ -109,9 +110,7 @@ __global__ void __launch_bounds__(256) k_bow_words(VocDev v, BowBatch b) {
 #pragma unroll
       for (int k = 0; k < kBowBatch; k++) {
         if (k < m) {
-          const int dd = __popc(a0.x ^ e0[k].x) + __popc(a0.y ^ e0[k].y) + __popc(a0.z ^ e0[k].z) +
-                         __popc(a0.w ^ e0[k].w) + __popc(a1.x ^ e1[k].x) + __popc(a1.y ^ e1[k].y) +
-                         __popc(a1.z ^ e1[k].z) + __popc(a1.w ^ e1[k].w);
+          const int dd = hamming256(a0, a1, e0[k], e1[k]);
           if (best < 0 || dd < bd) {
             bd = dd;
             best = c[k];

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/orbpl.h"
+#include "block_ops.h"
 #include "orbpl_runtime.h"
 #include "reloc_kernels.h"
 
@@ -57,11 +58,6 @@ __device__ __forceinline__ int find_word(const uint32_t* qw, int qn, uint32_t w)
     else hi = mid;
   }
   return (lo < qn && qw[lo] == w) ? lo : -1;
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
 }
 
 }  // namespace
@@ -192,7 +188,7 @@ __global__ void __launch_bounds__(kKfdbThreads) k_kfdb_reloc(KfdbArgs a) {
     }
     S.acc[lane] = accScore;
     S.best[lane] = bestKF;
-    wave_lds_sync();
+    lds_wave_sync();
     if (lane == 0) {
       float bestAcc = 0;
       for (int r = 0; r < nshare; r++)

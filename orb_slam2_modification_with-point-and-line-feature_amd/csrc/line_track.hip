@@ -11,6 +11,7 @@
 //   line map update: lives in k_finish (track_kernels.hip)
 #include <hip/hip_runtime.h>
 
+#include "block_ops.h"
 #include "line_common.h"
 #include "lsd_kernels.h"
 #include "track_common.h"
@@ -145,12 +146,7 @@ __device__ bool line_matching(const orbpl_keyline& k1, const orbpl_keyline& k2, 
                               const uint4* d2, const double off0, const double off1,
                               const double off2, const double off3) {
   const double kPi = 3.14159265358979323846;
-  int dist = 0;
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    const uint4 a = d1[q], b = d2[q];
-    dist += __popc(a.x ^ b.x) + __popc(a.y ^ b.y) + __popc(a.z ^ b.z) + __popc(a.w ^ b.w);
-  }
+  const int dist = hamming256(d1[0], d1[1], d2);
   if (dist > 45 + off3) return false;
   if (fabsf(k1.angle - k2.angle) > 15.0 * kPi / 180.0 + off0 * kPi / 180.0) return false;
   if (smin(k1.lineLength, k2.lineLength) / smax(k1.lineLength, k2.lineLength) < 0.45 + off1)
@@ -221,7 +217,6 @@ __global__ void __launch_bounds__(256) k_line_match(TrackConsts c, LineTrackArgs
   trk_priority();
   __shared__ orbpl_keyline s_kl[kLineKeep];
   __shared__ int s_src[kLineKeep];
-  __shared__ int s_np;
   __shared__ unsigned s_ok[kLineKeep][(kLineKeep + 31) / 32];
   __shared__ int s_cnt;
   const int s = blockIdx.x, t = threadIdx.x;
@@ -292,18 +287,13 @@ __global__ void __launch_bounds__(256) k_line_match(TrackConsts c, LineTrackArgs
   }
   // compaction keeps the projected lines in last-frame index order
   __shared__ int s_wc[4];
-  const unsigned long long m = __ballot(valid);
-  if ((t & 63) == 0) s_wc[t >> 6] = __popcll(m);
-  __syncthreads();
-  int pos = __popcll(m & ((1ull << (t & 63)) - 1ull));
-  for (int w = 0; w < (t >> 6); w++) pos += s_wc[w];
+  int np;
+  const int pos = block_prefix(valid, s_wc, &np);
   if (valid) {
     s_kl[pos] = k;
     s_src[pos] = t;
   }
-  if (t == 0) s_np = s_wc[0] + s_wc[1] + s_wc[2] + s_wc[3];
   __syncthreads();
-  const int np = s_np;
   const uint4* cur_desc = reinterpret_cast<const uint4*>(a.desc + lb * 32);
   const uint4* last_desc = reinterpret_cast<const uint4*>(a.last_desc + lb * 32);
   int total = 0;
@@ -377,9 +367,7 @@ __global__ void __launch_bounds__(128) k_stereo_lines(TrackConsts c, StereoLineA
     int best = 46;
     for (int j = 0; j < nr; j++) {
       const uint4 b0 = s_dr[2 * j], b1 = s_dr[2 * j + 1];
-      const int dist = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) +
-                       __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
-                       __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+      const int dist = hamming256(a0, a1, b0, b1);
       if (dist > 45 || dist >= best) continue;
       const orbpl_keyline& kb = s_kr[j];
       if (fabs((double)ka.angle - (double)kb.angle) > 10.0 * kPi / 180.0) continue;
@@ -456,7 +444,7 @@ __device__ __forceinline__ void line_list_stream(const TrackConsts& c, LineListA
   }
   __shared__ int s_np, s_cnt;
   __shared__ int s_last[kLineKeep];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   double T[12];
 #pragma unroll
   for (int q = 0; q < 12; q++) T[q] = a.Tcw[q];
@@ -466,17 +454,14 @@ __device__ __forceinline__ void line_list_stream(const TrackConsts& c, LineListA
     const int i = base + t;
     orbpl_keyline k{};
     const bool ok = i < a.nml && a.valid[i] && project_map_line(c, T, a.ml_xyz6 + (long long)i * 6, k);
-    const unsigned long long m = __ballot(ok);
-    if (lane == 0) s_wc[wave] = __popcll(m);
-    __syncthreads();
-    int pos = s_np + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; w++) pos += s_wc[w];
+    int tot;
+    const int pos = s_np + block_prefix(ok, s_wc, &tot);
     if (ok) {
       a.proj_kl[pos] = k;
       a.proj_src[pos] = i;
     }
     __syncthreads();
-    if (t == 0) s_np += s_wc[0] + s_wc[1] + s_wc[2] + s_wc[3];
+    if (t == 0) s_np += tot;
     __syncthreads();
   }
   const int np = s_np, ncur = min(a.ncur, kLineKeep);
@@ -545,7 +530,7 @@ __global__ void __launch_bounds__(256) k_line_pairs(TrackConsts c, LinePairArgs 
   __shared__ int s_wc[4];
   __shared__ int s_np, s_retry;
   __shared__ int s_cnobs[kLineKeep];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   double T[12];
 #pragma unroll
   for (int q = 0; q < 12; q++) T[q] = a.Tcw[q];
@@ -558,17 +543,14 @@ __global__ void __launch_bounds__(256) k_line_pairs(TrackConsts c, LinePairArgs 
     orbpl_keyline k{};
     if (i < a.nml && a.mode == 0 && a.base_kl) k = a.base_kl[i];
     const bool ok = i < a.nml && a.valid[i] && project_map_line(c, T, a.ml_xyz6 + (long long)i * 6, k);
-    const unsigned long long m = __ballot(ok);
-    if (lane == 0) s_wc[wave] = __popcll(m);
-    __syncthreads();
-    int pos = s_np + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; w++) pos += s_wc[w];
+    int tot;
+    const int pos = s_np + block_prefix(ok, s_wc, &tot);
     if (ok) {
       a.proj_kl[pos] = k;
       a.proj_src[pos] = i;
     }
     __syncthreads();
-    if (t == 0) s_np += s_wc[0] + s_wc[1] + s_wc[2] + s_wc[3];
+    if (t == 0) s_np += tot;
     __syncthreads();
   }
   const int np = s_np, words = (np + 31) >> 5;
@@ -648,9 +630,7 @@ __global__ void __launch_bounds__(256) k_line_bf_knn(int nq, const uint8_t* __re
     for (int j = 0; j < nt; j++) {
       const uint4* p = reinterpret_cast<const uint4*>(tdesc) + 2 * j;
       const uint4 p0 = p[0], p1 = p[1];
-      const int d = __popc(a0.x ^ p0.x) + __popc(a0.y ^ p0.y) + __popc(a0.z ^ p0.z) +
-                    __popc(a0.w ^ p0.w) + __popc(a1.x ^ p1.x) + __popc(a1.y ^ p1.y) +
-                    __popc(a1.z ^ p1.z) + __popc(a1.w ^ p1.w);
+      const int d = hamming256(a0, a1, p0, p1);
       if (b < 0 || d < db) {
         s = b;
         ds = db;

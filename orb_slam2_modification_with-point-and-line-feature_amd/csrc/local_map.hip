@@ -19,44 +19,13 @@
 // k_in_frustum / k_match_local / k_line_in_frustum / k_line_match_list.
 #include <hip/hip_runtime.h>
 
+#include "block_ops.h"
 #include "line_common.h"
 #include "lsd_kernels.h"
 #include "track_common.h"
 #include "track_kernels.h"
 
 namespace orbpl {
-
-namespace {
-
-// ordered block compaction: position of this thread's flagged element
-// (base + exclusive prefix over the block), the block total in *total
-__device__ __forceinline__ int block_prefix(bool flag, int* wsum, int* total) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const unsigned long long m = __ballot(flag);
-  if (lane == 0) wsum[wave] = __popcll(m);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < 4; w++) {
-    if (w < wave) off += wsum[w];
-    tot += wsum[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + __popcll(m & ((1ull << lane) - 1ull));
-}
-
-__device__ __forceinline__ int block_sum(int v, int* wsum) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  if (lane == 0) wsum[wave] = v;
-  __syncthreads();
-  const int r = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  __syncthreads();
-  return r;
-}
-
-}  // namespace
 
 __global__ void __launch_bounds__(256) k_lm_gather(LocalMapArgs a) {
   trk_priority();

@@ -27,6 +27,7 @@
 
 #include "line_common.h"
 #include "lsd_kernels.h"
+#include "block_ops.h"
 #include "map_kernels.h"
 #include "track_common.h"
 
@@ -36,53 +37,6 @@ namespace {
 
 constexpr int kT = 256;
 constexpr int kNotInit = 0, kOK = 1, kLost = 2;
-
-__device__ __forceinline__ int block_sum(int v, int* wsum) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  if (lane == 0) wsum[wave] = v;
-  __syncthreads();
-  const int r = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  __syncthreads();
-  return r;
-}
-
-// position of this thread's flagged element among the block's flagged ones
-// (thread order); the block's total in *total
-__device__ __forceinline__ int block_prefix(bool flag, int* wsum, int* total) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const unsigned long long m = __ballot(flag);
-  if (lane == 0) wsum[wave] = __popcll(m);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < 4; w++) {
-    if (w < wave) off += wsum[w];
-    tot += wsum[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + __popcll(m & ((1ull << lane) - 1ull));
-}
-
-// ascending bitonic sort of P (a power of two) keys in LDS
-__device__ void bitonic_sort(unsigned long long* keys, int P) {
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < P; i += kT) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], b = keys[ixj];
-          const bool up = (i & k) == 0;
-          if ((a > b) == up) {
-            keys[i] = b;
-            keys[ixj] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-}
 
 // libstdc++'s std::sort (introsort, median-of-3 pivot to first, unguarded
 // partition, heap sort below the depth limit, final insertion sort) of (key,
@@ -228,18 +182,6 @@ __device__ inline void unproject_f(const TrackConsts& c, const float* T, const f
   gemm_Rt_x_plus_c(T, x3, Ow, w);
 }
 
-__device__ inline int popc32(const uint8_t* a, const uint8_t* b) {
-  const uint4* p = reinterpret_cast<const uint4*>(a);
-  const uint4* q = reinterpret_cast<const uint4*>(b);
-  int d = 0;
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const uint4 x = p[k], y = q[k];
-    d += __popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w);
-  }
-  return d;
-}
-
 __device__ inline void copy32(uint8_t* d, const uint8_t* s) {
   reinterpret_cast<uint4*>(d)[0] = reinterpret_cast<const uint4*>(s)[0];
   reinterpret_cast<uint4*>(d)[1] = reinterpret_cast<const uint4*>(s)[1];
@@ -338,9 +280,7 @@ __device__ void compute_distinctive(const MapArgs& a, const Pools& P, int p, uin
           const int j = j0 + q;
           if (j >= nob) break;
           const uint4 u = y[2 * q], v = y[2 * q + 1];
-          const int d = __popc(x0.x ^ u.x) + __popc(x0.y ^ u.y) + __popc(x0.z ^ u.z) +
-                        __popc(x0.w ^ u.w) + __popc(x1.x ^ v.x) + __popc(x1.y ^ v.y) +
-                        __popc(x1.z ^ v.z) + __popc(x1.w ^ v.w);
+          const int d = hamming256(x0, x1, u, v);
           dscr[j] = (uint16_t)(i == j ? 0 : d);
         }
       }
@@ -515,7 +455,7 @@ __global__ void __launch_bounds__(kT) k_map_begin(TrackConsts c, MapArgs a) {
   }
   nv = block_sum(nv, wsum);
   if (nv == 0) return;   // "if(vDepthIdx.empty()) return;" (lines included)
-  bitonic_sort(keys, Pn);
+  bitonic_sort(keys, Pn, kT);
   const float thd = c.th_depth;
   for (int j = t; j < nv; j += kT) {
     const float z = __uint_as_float((unsigned)(keys[j] >> 32));
@@ -1259,7 +1199,7 @@ __global__ void __launch_bounds__(kT) k_map_finish(TrackConsts c, MapArgs a) {
         }
         if (t == 0) s_i[1] = 0x7fffffff;
         nv = block_sum(nv, wsum);
-        bitonic_sort(keys, Pn);
+        bitonic_sort(keys, Pn, kT);
         for (int j = t; j < nv; j += kT) {
           const float z = __uint_as_float((unsigned)(keys[j] >> 32));
           if (z > c.th_depth && j + 1 > 100) atomicMin(&s_i[1], j);

@@ -23,7 +23,9 @@
 
 #include <cstdlib>
 
+#include "block_ops.h"
 #include "lsd_math.h"
+#include "match_common.h"
 #include "track_common.h"
 #include "track_kernels.h"
 #include "orbpl_runtime.h"
@@ -144,31 +146,12 @@ struct Top2 {
 // entry = distance << 23 | scan key (all ones = empty: no candidate has
 // distance 255 and row 63); bit 31 of the last entry flags more candidates than
 // the list holds.
-constexpr int kTopK = 4;
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
 constexpr uint32_t kMore = 0x80000000u;
 
 struct TopList {
   uint32_t e[kTopK];
 };
-
-__device__ __forceinline__ int hamming32l(const uint8_t* a, const uint8_t* b) {
-  const uint4 a0 = *reinterpret_cast<const uint4*>(a);
-  const uint4 a1 = *reinterpret_cast<const uint4*>(a + 16);
-  const uint4 b0 = *reinterpret_cast<const uint4*>(b);
-  const uint4 b1 = *reinterpret_cast<const uint4*>(b + 16);
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-// the wave's LDS operations so far are complete and the compiler moves no
-// memory access across (one wave: LDS executes its operations in order). Unlike
-// a workgroup fence it does not wait for the wave's outstanding global loads
-// (phase B's next-chunk prefetch).
-__device__ __forceinline__ void lds_wave_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
 
 template <int KP>
 __device__ __forceinline__ bool is_claimed(const LocalShared<KP>& S, int j) {
@@ -192,11 +175,8 @@ __device__ TopList local_scan(const LocalShared<KP>& S, const TrackConsts& c, co
   if (a.th != 1.0) r *= a.th;
   const float rad = r * c.scale[lev];
   const float x = a.proj_x[i], y = a.proj_y[i], xr = a.proj_xr[i];
-  const int cx0 = max(0, (int)floorf((x - c.minX - rad) * c.gridInvW));
-  const int cx1 = min(kGridCols - 1, (int)ceilf((x - c.minX + rad) * c.gridInvW));
-  const int cy0 = max(0, (int)floorf((y - c.minY - rad) * c.gridInvH));
-  const int cy1 = min(kGridRows - 1, (int)ceilf((y - c.minY + rad) * c.gridInvH));
-  if (cx0 >= kGridCols || cx1 < 0 || cy0 >= kGridRows || cy1 < 0) return t;
+  int cx0, cx1, cy0, cy1;
+  if (!grid_window(c, x, y, rad, &cx0, &cx1, &cy0, &cy1)) return t;
   const uint4* dp = reinterpret_cast<const uint4*>(a.mp_desc + (long long)i * 32);
   const uint4 m0 = dp[0], m1 = dp[1];
   // octaves lev-1 and lev (bCheckLevels always holds: maxLevel = lev >= 0)
@@ -219,9 +199,7 @@ __device__ TopList local_scan(const LocalShared<KP>& S, const TrackConsts& c, co
       const uint4* cd = reinterpret_cast<const uint4*>(a.desc + (long long)j * 32);
       const uint4 c0 = cd[0], c1 = cd[1];
 #endif
-      const uint32_t dist = __popc(m0.x ^ c0.x) + __popc(m0.y ^ c0.y) + __popc(m0.z ^ c0.z) +
-                            __popc(m0.w ^ c0.w) + __popc(m1.x ^ c1.x) + __popc(m1.y ^ c1.y) +
-                            __popc(m1.z ^ c1.z) + __popc(m1.w ^ c1.w);
+      const uint32_t dist = hamming256(m0, m1, c0, c1);
       if (dist >= 256) continue;   // never below the initial 256 of either slot
       cnt++;
       // sorted insert: the list stays ascending in (distance, scan key)
@@ -547,22 +525,6 @@ void launch_match_local(const TrackConsts& c, const LocalArgs& a, hipStream_t s,
 // ---------------------------------------------------------------------------
 namespace {
 constexpr int kBowMax = 2048;
-__device__ void bitonic_sort(uint32_t* a, int n) {
-  for (int k = 2; k <= n; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int l = i ^ j;
-        if (l > i) {
-          const uint32_t x = a[i], y = a[l];
-          if (((i & k) == 0) ? (x > y) : (x < y)) {
-            a[i] = y;
-            a[l] = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
-}
 }  // namespace
 
 // LDS of one SearchByBoW instance for frames of up to CAP features: both
@@ -577,12 +539,6 @@ struct BowShared {
   int hist[32];
   int s_n, s_ind[3];
 };
-
-__device__ __forceinline__ int hamming32(const uint4 k0, const uint4 k1, const uint4 f0,
-                                         const uint4 f1) {
-  return __popc(k0.x ^ f0.x) + __popc(k0.y ^ f0.y) + __popc(k0.z ^ f0.z) + __popc(k0.w ^ f0.w) +
-         __popc(k1.x ^ f1.x) + __popc(k1.y ^ f1.y) + __popc(k1.z ^ f1.z) + __popc(k1.w ^ f1.w);
-}
 
 // [fb, fe) of the frame features of `node` in the sorted list sf (sentinels
 // 0xFFFFFFFF sort above every node: node ids are < 2^21 - 1)
@@ -637,8 +593,8 @@ __device__ void match_bow_body(const BowArgs& a, BowShared<CAP>& B, const uint4*
   // leaves the same runs
   int ns = 64;
   while (ns < nkf || ns < nf) ns <<= 1;
-  bitonic_sort(B.skf, ns);
-  bitonic_sort(B.sf, ns);
+  bitonic_sort(B.skf, ns, blockDim.x);
+  bitonic_sort(B.sf, ns, blockDim.x);
   const uint4* fd = reinterpret_cast<const uint4*>(a.f_desc);
   const uint4* kd = reinterpret_cast<const uint4*>(a.kf_desc);
   // 2. candidate lists, one keyframe feature per lane
@@ -655,7 +611,7 @@ __device__ void match_bow_body(const BowArgs& a, BowShared<CAP>& B, const uint4*
         const uint32_t iF = B.sf[r] & 0x7FF;
         const uint4 f0 = fdl ? fdl[2 * iF] : fd[2 * iF];
         const uint4 f1 = fdl ? fdl[2 * iF + 1] : fd[2 * iF + 1];
-        const int d = hamming32(k0, k1, f0, f1);
+        const int d = hamming256(k0, k1, f0, f1);
         // a distance of 256 never beats the reference's initial 256
         const uint32_t k = d < 256 ? ((uint32_t)d << 11) | iF : 0xFFFFFFFFu;
         // sorted insertion (frame indices ascend along the run: ties keep order)
@@ -709,7 +665,7 @@ __device__ void match_bow_body(const BowArgs& a, BowShared<CAP>& B, const uint4*
         for (int r = fb; r < fe; r++) {
           const int iF = (int)(B.sf[r] & 0x7FF);
           if (B.smatch[iF] >= 0) continue;
-          const int dist = hamming32(k0, k1, fdl ? fdl[2 * iF] : fd[2 * iF],
+          const int dist = hamming256(k0, k1, fdl ? fdl[2 * iF] : fd[2 * iF],
                                      fdl ? fdl[2 * iF + 1] : fd[2 * iF + 1]);
           if (dist < bestDist1) {
             bestDist2 = bestDist1;
@@ -723,11 +679,8 @@ __device__ void match_bow_body(const BowArgs& a, BowShared<CAP>& B, const uint4*
       if (bestDist1 <= 50 && static_cast<float>(bestDist1) < a.nnratio * static_cast<float>(bestDist2)) {
         B.smatch[bestIdxF] = (int16_t)iKF;
         if (a.check_ori) {
-          float rot = a.kf_angle[(long long)iKF * a.kf_angle_stride] -
-                      a.f_angle[(long long)bestIdxF * a.f_angle_stride];
-          if (rot < 0.0f) rot += 360.0f;
-          int bin = (int)roundf(rot * (30 / 360.0f));
-          if (bin == 30) bin = 0;
+          const int bin = rotation_bin(a.kf_angle[(long long)iKF * a.kf_angle_stride],
+                                       a.f_angle[(long long)bestIdxF * a.f_angle_stride]);
           B.sbin[bestIdxF] = (int8_t)bin;
           atomicAdd(&B.hist[bin], 1);
         }
@@ -740,22 +693,8 @@ __device__ void match_bow_body(const BowArgs& a, BowShared<CAP>& B, const uint4*
   // 4. rotation consistency (ORBmatcher.cc:2035-2077, :386-404)
   if (a.check_ori) {
     if (t == 0) {
-      int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-      for (int i = 0; i < 30; i++) {
-        const int sz = B.hist[i];
-        if (sz > max1) {
-          max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i;
-        } else if (sz > max2) {
-          max3 = max2; max2 = sz; ind3 = ind2; ind2 = i;
-        } else if (sz > max3) {
-          max3 = sz; ind3 = i;
-        }
-      }
-      if (max2 < 0.1f * (float)max1) {
-        ind2 = -1; ind3 = -1;
-      } else if (max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-      }
+      int ind1, ind2, ind3;
+      three_maxima(B.hist, ind1, ind2, ind3);
       B.s_ind[0] = ind1; B.s_ind[1] = ind2; B.s_ind[2] = ind3;
     }
     __syncthreads();
@@ -898,6 +837,8 @@ struct KfShared {
   int misc[8];
 };
 static_assert(1024 * kTopK >= kGridCols * kGridRows, "top[] doubles as cell fill counters");
+static_assert(sizeof(KfShared<1024>) == 63928 && sizeof(KfShared<2048>) == 115384,
+              "LDS per workgroup decides how many problems share a CU");
 
 struct KfProj {
   bool ok;
@@ -939,12 +880,7 @@ __device__ KfProj kf_project(const TrackConsts& c, const MatchKfArgs& a, const f
   p.radius = r;
   p.minLevel = lev - 1;
   p.maxLevel = lev + 1;
-  p.cx0 = max(0, (int)floorf((u - c.minX - r) * c.gridInvW));
-  p.cx1 = min(kGridCols - 1, (int)ceilf((u - c.minX + r) * c.gridInvW));
-  p.cy0 = max(0, (int)floorf((v - c.minY - r) * c.gridInvH));
-  p.cy1 = min(kGridRows - 1, (int)ceilf((v - c.minY + r) * c.gridInvH));
-  if (p.cx0 >= kGridCols || p.cx1 < 0 || p.cy0 >= kGridRows || p.cy1 < 0) return p;
-  p.ok = true;
+  p.ok = grid_window(c, u, v, r, &p.cx0, &p.cx1, &p.cy0, &p.cy1);
   return p;
 }
 
@@ -970,11 +906,13 @@ __device__ int kf_scan(const KfShared<KMAX>& S, const KfProj& p, const uint8_t* 
       const float2 xy = S.xy[j];
       if (!(fabsf(xy.x - p.u) < r && fabsf(xy.y - p.v) < r)) continue;
       if ((S.claimed[j >> 5] >> (j & 31)) & 1u) continue;
-      const int dist = hamming32l(dMP, cdesc + (long long)j * 32);
+      const int dist = hamming256(dMP, cdesc + (long long)j * 32);
       if (dist > orbd) continue;
       cnt++;
       int v = (dist << 16) | j;
-      // stable insertion: equal distances keep scan order
+      // stable insertion: equal distances keep scan order. topk_insert()
+      // written out: through the helper the kernel measured 2.4 % slower on
+      // one problem (profiles/r08/refactor_ab.txt)
       bool ins = false;
 #pragma unroll
       for (int q2 = 0; q2 < kTopK; q2++) {
@@ -1009,77 +947,25 @@ __global__ void __launch_bounds__(256) k_match_kf(TrackConsts c, MatchKfArgs a) 
   // beats the initial bestDist = 256, so ORBdist acts within [-1, 255]
   const int orbd = min(max(a.orb_dist, -1), 255);
   // ---- current frame into LDS + grid (AssignFeaturesToGrid, Frame.cc:265-287) ----
-  for (int i = t; i < kGridCols * kGridRows; i += NT) S.cell_start[i] = 0;
   for (int i = t; i < KMAX / 32; i += NT) {
     S.claimed[i] = 0;
     S.removed[i] = 0;
   }
   if (t < 32) S.hist[t] = 0;
-  __syncthreads();
-  for (int i = t; i < n; i += NT) {
+  // (the grid build's first barrier orders these before the claims below)
+  build_frame_grid<NT>(S.cell_start, S.items, S.gc, S.top, S.wsum, n, [&](int i) {
     const KeyPointD k = ck[i];
     S.xy[i] = make_float2(k.x, k.y);
     S.ang[i] = k.angle;
     S.oct[i] = (int8_t)k.octave;
     S.mpw[i] = -1;
     S.fc[i] = 0x7fffffff;
+    if (a.cur_has_mp[cb + i]) atomicOr(&S.claimed[i >> 5], 1u << (i & 31));
     // Frame::PosInGrid (Frame.cc:527-538)
     const int px = (int)roundf((k.x - c.minX) * c.gridInvW);
     const int py = (int)roundf((k.y - c.minY) * c.gridInvH);
-    const int g = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? -1 : px * kGridRows + py;
-    S.gc[i] = (int16_t)g;
-    if (g >= 0) atomicAdd(&S.cell_start[g], 1);
-    if (a.cur_has_mp[cb + i]) atomicOr(&S.claimed[i >> 5], 1u << (i & 31));
-  }
-  __syncthreads();
-  {  // exclusive scan of the 3072 cell counts
-    constexpr int kPer = (kGridCols * kGridRows) / NT;
-    int loc[kPer];
-    int sum = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; k++) {
-      loc[k] = S.cell_start[t * kPer + k];
-      sum += loc[k];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
-    }
-    if (lane == 63) S.wsum[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; w++) base += S.wsum[w];
-    int run = base + incl - sum;
-#pragma unroll
-    for (int k = 0; k < kPer; k++) {
-      S.cell_start[t * kPer + k] = run;
-      S.top[t * kPer + k] = run;   // fill counter
-      run += loc[k];
-    }
-    if (t == NT - 1) S.cell_start[kGridCols * kGridRows] = run;
-    __syncthreads();
-  }
-  for (int i = t; i < n; i += NT) {
-    const int g = S.gc[i];
-    if (g >= 0) S.items[atomicAdd(&S.top[g], 1)] = (uint16_t)i;
-  }
-  __syncthreads();
-  // mGrid[ix][iy] holds its keypoints in increasing index order
-  for (int cell = t; cell < kGridCols * kGridRows; cell += NT) {
-    const int b = S.cell_start[cell], e = S.cell_start[cell + 1];
-    for (int q = b + 1; q < e; q++) {
-      const uint16_t v = S.items[q];
-      int r = q - 1;
-      while (r >= b && S.items[r] > v) {
-        S.items[r + 1] = S.items[r];
-        r--;
-      }
-      S.items[r + 1] = v;
-    }
-  }
-  __syncthreads();
+    return (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? -1 : px * kGridRows + py;
+  });
   float Ow[3];
   gemm_neg_Rt_t(Tc, Ow);
   // ---- phase A ----
@@ -1109,11 +995,7 @@ __global__ void __launch_bounds__(256) k_match_kf(TrackConsts c, MatchKfArgs a) 
       auto commit = [&](int k) {
         S.mpw[k] = i;
         atomicOr(&S.claimed[k >> 5], 1u << (k & 31));
-        float rot = a.kf_angle[kb + i] - S.ang[k];
-        if (rot < 0.0f) rot += 360.0f;
-        int b = (int)roundf(rot * (30 / 360.0f));
-        if (b == 30) b = 0;
-        S.bin[i] = b;
+        S.bin[i] = rotation_bin(a.kf_angle[kb + i], S.ang[k]);
         S.sel[i] = k;
         acc++;
       };
@@ -1159,45 +1041,7 @@ __global__ void __launch_bounds__(256) k_match_kf(TrackConsts c, MatchKfArgs a) 
   __syncthreads();
   int nmatches = S.misc[0];
   // ---- phase C: rotation consistency (ORBmatcher.cc:2001-2021, 2035-2077) ----
-  if (a.check_ori) {
-    for (int i = t; i < nk; i += NT)
-      if (S.bin[i] >= 0) atomicAdd(&S.hist[S.bin[i]], 1);
-    __syncthreads();
-    if (t == 0) {
-      int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-      for (int i = 0; i < 30; i++) {
-        const int sz = S.hist[i];
-        if (sz > max1) {
-          max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i;
-        } else if (sz > max2) {
-          max3 = max2; max2 = sz; ind3 = ind2; ind2 = i;
-        } else if (sz > max3) {
-          max3 = sz; ind3 = i;
-        }
-      }
-      if (max2 < 0.1f * (float)max1) {
-        ind2 = -1; ind3 = -1;
-      } else if (max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-      }
-      S.misc[1] = ind1; S.misc[2] = ind2; S.misc[3] = ind3;
-      S.misc[4] = 0;
-    }
-    __syncthreads();
-    const int ind1 = S.misc[1], ind2 = S.misc[2], ind3 = S.misc[3];
-    int nrem = 0;
-    for (int i = t; i < nk; i += NT) {
-      const int b = S.bin[i];
-      if (b >= 0 && b != ind1 && b != ind2 && b != ind3) {
-        const int k = S.sel[i];
-        atomicOr(&S.removed[k >> 5], 1u << (k & 31));
-        nrem++;
-      }
-    }
-    if (nrem) atomicAdd(&S.misc[4], nrem);
-    __syncthreads();
-    nmatches -= S.misc[4];
-  }
+  if (a.check_ori) nmatches -= rotation_filter<NT>(S.bin, S.sel, nk, S.hist, S.removed, S.misc);
   for (int i = t; i < n; i += NT) {
     int m = S.mpw[i];
     if (a.check_ori && ((S.removed[i >> 5] >> (i & 31)) & 1u)) m = -1;

@@ -15,6 +15,7 @@
 
 #include <climits>
 
+#include "block_ops.h"
 #include "orb_geom.h"
 #include "track_common.h"
 #include "track_kernels.h"
@@ -26,32 +27,6 @@ namespace {
 constexpr int kStereoKp = 4096;
 constexpr int kStereoRows = 1024;
 
-__device__ __forceinline__ int ham32(const uint8_t* a, const uint8_t* b) {
-  const uint4 a0 = *reinterpret_cast<const uint4*>(a);
-  const uint4 a1 = *reinterpret_cast<const uint4*>(a + 16);
-  const uint4 b0 = *reinterpret_cast<const uint4*>(b);
-  const uint4 b1 = *reinterpret_cast<const uint4*>(b + 16);
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-__device__ void bitonic_u32(uint32_t* a, int n) {
-  for (int k = 2; k <= n; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int l = i ^ j;
-        if (l > i) {
-          const uint32_t x = a[i], y = a[l];
-          if (((i & k) == 0) ? (x > y) : (x < y)) {
-            a[i] = y;
-            a[l] = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
-}
-
 }  // namespace
 
 __global__ void __launch_bounds__(256) k_stereo(StereoArgs a) {
@@ -59,7 +34,7 @@ __global__ void __launch_bounds__(256) k_stereo(StereoArgs a) {
   __shared__ int row_fill[kStereoRows];
   __shared__ uint32_t keys[kStereoKp];
   __shared__ int s_cnt, s_wsum[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   const int f = blockIdx.x;
   // this frame's slice of the batch (locals: the kernel argument stays
   // read-only, so its level table is never copied to scratch)
@@ -87,32 +62,7 @@ __global__ void __launch_bounds__(256) k_stereo(StereoArgs a) {
     for (int yi = max(minr, 0); yi <= min(maxr, nRows - 1); yi++) atomicAdd(&row_start[yi], 1);
   }
   __syncthreads();
-  {  // exclusive scan of kStereoRows counts, 4 per thread
-    int loc[4], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      loc[k] = row_start[t * 4 + k];
-      sum += loc[k];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    int run = incl - sum;
-    for (int w = 0; w < wave; w++) run += s_wsum[w];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      row_start[t * 4 + k] = run;
-      row_fill[t * 4 + k] = run;
-      run += loc[k];
-    }
-    if (t == 255) row_start[kStereoRows] = run;
-    __syncthreads();
-  }
+  block_exclusive_scan<kStereoRows / 256, 256>(row_start, s_wsum, row_fill);
   const int total = row_start[kStereoRows];
   if (total > a.entry_cap) {
     if (t == 0) *a.err = 1;
@@ -163,7 +113,7 @@ __global__ void __launch_bounds__(256) k_stereo(StereoArgs a) {
       if (kpR.octave < levelL - 1 || kpR.octave > levelL + 1) continue;
       const float uR = kpR.x;
       if (uR >= minU && uR <= maxU) {
-        const int dist = ham32(dL, a_dr + (long long)iR * 32);
+        const int dist = hamming256(dL, a_dr + (long long)iR * 32);
         if (dist < bestDist) {
           bestDist = dist;
           bestIdxR = iR;
@@ -250,7 +200,7 @@ __global__ void __launch_bounds__(256) k_stereo(StereoArgs a) {
     keys[i] = d >= 0 ? ((uint32_t)d << 12) | (uint32_t)i : 0xFFFFFFFFu;
   }
   __syncthreads();
-  bitonic_u32(keys, kStereoKp);
+  bitonic_sort(keys, kStereoKp, blockDim.x);
   const float median = (float)(int)(keys[cnt / 2] >> 12);
   const float thDist = 1.5f * 1.4f * median;
   for (int iL = t; iL < n; iL += 256) {

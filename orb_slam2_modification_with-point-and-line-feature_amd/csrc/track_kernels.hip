@@ -23,6 +23,8 @@
 #include <stdint.h>
 
 #include "orbpl_math.h"
+#include "block_ops.h"
+#include "match_common.h"
 #include "track_common.h"
 #include "track_kernels.h"
 #include "lsd_kernels.h"
@@ -133,22 +135,6 @@ struct MatchArgs {
 // SearchByProjection: [0] grid, [1] phase A, [2] phase B, [3] phase C, [4] output
 __device__ long long g_match_prof[8];
 
-__device__ __forceinline__ int hamming32(const uint8_t* a, const uint8_t* b) {
-  const uint4 a0 = *reinterpret_cast<const uint4*>(a);
-  const uint4 a1 = *reinterpret_cast<const uint4*>(a + 16);
-  const uint4 b0 = *reinterpret_cast<const uint4*>(b);
-  const uint4 b1 = *reinterpret_cast<const uint4*>(b + 16);
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-// Hamming distance of a descriptor held in registers and one in LDS
-__device__ __forceinline__ int hamming_rl(uint4 a0, uint4 a1, const uint4* b) {
-  const uint4 b0 = b[0], b1 = b[1];
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 // Current-frame descriptors staged in LDS for KMAX <= ORBPL_MATCH_DESC_LDS_MAX
 // (32 KB at 1024 keypoints), else read from global memory (L2). Default 0:
 // from global memory for every KMAX - the smaller workgroup is placed sooner
@@ -197,13 +183,7 @@ __device__ __forceinline__ ProjInfo project_point(const TrackConsts& c, const fl
     p.minLevel = nLastOctave - 1;
     p.maxLevel = nLastOctave + 1;
   }
-  const float r = p.radius;
-  p.cx0 = max(0, (int)floorf((u - c.minX - r) * c.gridInvW));
-  p.cx1 = min(kGridCols - 1, (int)ceilf((u - c.minX + r) * c.gridInvW));
-  p.cy0 = max(0, (int)floorf((v - c.minY - r) * c.gridInvH));
-  p.cy1 = min(kGridRows - 1, (int)ceilf((v - c.minY + r) * c.gridInvH));
-  if (p.cx0 >= kGridCols || p.cx1 < 0 || p.cy0 >= kGridRows || p.cy1 < 0) return p;
-  p.ok = true;
+  p.ok = grid_window(c, u, v, p.radius, &p.cx0, &p.cx1, &p.cy0, &p.cy1);
   return p;
 }
 
@@ -241,8 +221,8 @@ __device__ int scan_best(const SH& S, const TrackConsts& c, const ProjInfo& p,
         if (er > p.radius) continue;
       }
       int dist;
-      if constexpr (kLdsDesc) dist = hamming_rl(m0, m1, &S.desc[2 * j]);
-      else dist = hamming32(dMP, cur_desc + (long long)j * 32);
+      if constexpr (kLdsDesc) dist = hamming256(m0, m1, &S.desc[2 * j]);
+      else dist = hamming256(dMP, cur_desc + (long long)j * 32);
       if (dist < bestDist) {
         bestDist = dist;
         bestIdx = j;
@@ -252,7 +232,6 @@ __device__ int scan_best(const SH& S, const TrackConsts& c, const ProjInfo& p,
   return bestIdx < 0 ? -1 : ((bestDist << 16) | bestIdx);
 }
 
-constexpr int kTopK = 4;
 // k_match_last block size: one block per stream. The kernel takes up to
 // kMatchThreads; it launches with kMatchLaunchThreads: in pipelined tracking it
 // shares the CUs with the next batch's extraction, and a 4-wave workgroup is
@@ -285,6 +264,8 @@ struct MatchShared {
   int misc[8];
 };
 static_assert(kMatchMaxKp * kTopK >= kGridCols * kGridRows, "top[] doubles as cell fill counters");
+static_assert(sizeof(MatchShared<1024>) == 68096 && sizeof(MatchShared<2048>) == 123648,
+              "LDS per workgroup decides how many streams share a CU");
 
 template <int KMAX, int NT>
 __global__ void __launch_bounds__(NT) k_match_last(TrackConsts c, MatchArgs a) {
@@ -317,14 +298,17 @@ __global__ void __launch_bounds__(NT) k_match_last(TrackConsts c, MatchArgs a) {
   const float* Tc = a.Tcw + (long long)s * a.pose_stride;
   const float* Tl = a.Tlw + (long long)s * a.pose_stride;
   // ---- current frame into LDS + grid (AssignFeaturesToGrid, Frame.cc:265-287) ----
-  for (int i = t; i < kGridCols * kGridRows; i += NT) S.cell_start[i] = 0;
-  __syncthreads();
-  for (int i = t; i < n; i += NT) {
+  build_frame_grid<NT>(S.cell_start, S.items, S.gc, S.top, S.wsum, n, [&](int i) {
     const KeyPointD k = ck[i];
     S.xy[i] = make_float2(k.x, k.y);
     S.ang[i] = k.angle;
     S.oct[i] = (int8_t)k.octave;
     S.ur[i] = a.cur_uright[cb + i];
+    if constexpr (match_desc_lds(KMAX)) {
+      const uint4* dsrc = reinterpret_cast<const uint4*>(cdesc + (long long)i * 32);
+      S.desc[2 * i] = dsrc[0];
+      S.desc[2 * i + 1] = dsrc[1];
+    }
     int g;
     if (a.cur_gcell) {
       g = a.cur_gcell[cb + i];
@@ -333,65 +317,8 @@ __global__ void __launch_bounds__(NT) k_match_last(TrackConsts c, MatchArgs a) {
       const int py = (int)roundf((k.y - c.minY) * c.gridInvH);
       g = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? -1 : px + kGridCols * py;
     }
-    if (g >= 0) g = (g % kGridCols) * kGridRows + g / kGridCols;   // column-major cell
-    S.gc[i] = (int16_t)g;
-    if (g >= 0) atomicAdd(&S.cell_start[g], 1);
-    if constexpr (match_desc_lds(KMAX)) {
-      const uint4* dsrc = reinterpret_cast<const uint4*>(cdesc + (long long)i * 32);
-      S.desc[2 * i] = dsrc[0];
-      S.desc[2 * i + 1] = dsrc[1];
-    }
-  }
-  __syncthreads();
-  {  // exclusive scan of the 3072 cell counts (kPer per thread)
-    constexpr int kPer = (kGridCols * kGridRows) / NT;
-    int loc[kPer];
-    int sum = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; k++) {
-      loc[k] = S.cell_start[t * kPer + k];
-      sum += loc[k];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      int u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
-    }
-    if (lane == 63) S.wsum[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; w++) base += S.wsum[w];
-    int run = base + incl - sum;
-#pragma unroll
-    for (int k = 0; k < kPer; k++) {
-      S.cell_start[t * kPer + k] = run;
-      S.top[t * kPer + k] = run;  // fill counter
-      run += loc[k];
-    }
-    if (t == NT - 1) S.cell_start[kGridCols * kGridRows] = run;
-    __syncthreads();
-  }
-  // place items (any order), then sort each cell by index: the reference's
-  // mGrid[ix][iy] vectors hold indices in increasing order
-  for (int i = t; i < n; i += NT) {
-    const int g = S.gc[i];
-    if (g >= 0) S.items[atomicAdd(&S.top[g], 1)] = (uint16_t)i;
-  }
-  __syncthreads();
-  for (int cell = t; cell < kGridCols * kGridRows; cell += NT) {
-    const int b = S.cell_start[cell], e = S.cell_start[cell + 1];
-    for (int q = b + 1; q < e; q++) {
-      const uint16_t v = S.items[q];
-      int r = q - 1;
-      while (r >= b && S.items[r] > v) {
-        S.items[r + 1] = S.items[r];
-        r--;
-      }
-      S.items[r + 1] = v;
-    }
-  }
-  __syncthreads();
+    return g >= 0 ? (g % kGridCols) * kGridRows + g / kGridCols : -1;   // column-major cell
+  });
   lap(0);
   // ---- forward/backward motion (ORBmatcher.cc:1724-1744) ----
   float twc[3], tlc[3];
@@ -436,24 +363,11 @@ __global__ void __launch_bounds__(NT) k_match_last(TrackConsts c, MatchArgs a) {
               const float urj = S.ur[j];
               if (urj > 0 && fabsf(urp - urj) > p.radius) continue;
               int dist;
-              if constexpr (match_desc_lds(KMAX)) dist = hamming_rl(m0, m1, &S.desc[2 * j]);
-              else dist = hamming32(dMP, cdesc + (long long)j * 32);
+              if constexpr (match_desc_lds(KMAX)) dist = hamming256(m0, m1, &S.desc[2 * j]);
+              else dist = hamming256(dMP, cdesc + (long long)j * 32);
               if (dist > 100) continue;
               cnt++;
-              int v = (dist << 16) | j;
-              // stable insertion: equal distances keep scan order; once
-              // inserted, the displaced entries shift down one place each
-              bool ins = false;
-#pragma unroll
-              for (int q2 = 0; q2 < kTopK; q2++) {
-                const int cur = tk[q2];
-                if (ins || cur < 0 || (v >> 16) < (cur >> 16)) {
-                  tk[q2] = v;
-                  v = cur;
-                  ins = true;
-                  if (v < 0) break;
-                }
-              }
+              topk_insert(tk, (dist << 16) | j);
             }
           }
         }
@@ -518,11 +432,7 @@ __global__ void __launch_bounds__(NT) k_match_last(TrackConsts c, MatchArgs a) {
             if (choice >= 0) {
               atomicMax(&S.mpw[choice], i);
               if (claimer) atomicOr(&S.claimed[choice >> 5], 1u << (choice & 31));
-              float rot = a.last_kps_un[li].angle - S.ang[choice];
-              if (rot < 0.0f) rot += 360.0f;
-              int b = (int)roundf(rot * (30 / 360.0f));
-              if (b == 30) b = 0;
-              S.bin[i] = b;
+              S.bin[i] = rotation_bin(a.last_kps_un[li].angle, S.ang[choice]);
               S.sel[i] = choice;
               acc++;
             }
@@ -534,17 +444,12 @@ __global__ void __launch_bounds__(NT) k_match_last(TrackConsts c, MatchArgs a) {
             // all kTopK candidates taken: full re-scan excluding taken ones
             const ProjInfo pj = project_point(c, Tc, a.last_xyz + li * 3, a.last_kps_un[li].octave,
                                               th, bForward, bBackward);
-            const int r = scan_best<match_desc_lds(KMAX)>(S, c, pj, a.last_desc + li * 32, cdesc,
-                                                          true, mbf);
+            const int r = scan_best<match_desc_lds(KMAX)>(S, c, pj, a.last_desc + li * 32, cdesc, true, mbf);
             if (r >= 0 && (r >> 16) <= 100) {
               const int k = r & 0xFFFF;
               atomicMax(&S.mpw[k], i);
               if (claimer) atomicOr(&S.claimed[k >> 5], 1u << (k & 31));
-              float rot = a.last_kps_un[li].angle - S.ang[k];
-              if (rot < 0.0f) rot += 360.0f;
-              int b = (int)roundf(rot * (30 / 360.0f));
-              if (b == 30) b = 0;
-              S.bin[i] = b;
+              S.bin[i] = rotation_bin(a.last_kps_un[li].angle, S.ang[k]);
               S.sel[i] = k;
               acc++;
             }
@@ -562,45 +467,7 @@ __global__ void __launch_bounds__(NT) k_match_last(TrackConsts c, MatchArgs a) {
     lap(2);
     nmatches = S.misc[0];
     // ---- phase C: rotation consistency (ORBmatcher.cc:1850-1876, 2035-2077) ----
-    if (a.check_ori) {
-      for (int i = t; i < nl; i += NT)
-        if (S.bin[i] >= 0) atomicAdd(&S.hist[S.bin[i]], 1);
-      __syncthreads();
-      if (t == 0) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < 30; i++) {
-          const int sz = S.hist[i];
-          if (sz > max1) {
-            max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i;
-          } else if (sz > max2) {
-            max3 = max2; max2 = sz; ind3 = ind2; ind2 = i;
-          } else if (sz > max3) {
-            max3 = sz; ind3 = i;
-          }
-        }
-        if (max2 < 0.1f * (float)max1) {
-          ind2 = -1; ind3 = -1;
-        } else if (max3 < 0.1f * (float)max1) {
-          ind3 = -1;
-        }
-        S.misc[1] = ind1; S.misc[2] = ind2; S.misc[3] = ind3;
-        S.misc[4] = 0;
-      }
-      __syncthreads();
-      const int ind1 = S.misc[1], ind2 = S.misc[2], ind3 = S.misc[3];
-      int nrem = 0;
-      for (int i = t; i < nl; i += NT) {
-        const int b = S.bin[i];
-        if (b >= 0 && b != ind1 && b != ind2 && b != ind3) {
-          const int k = S.sel[i];
-          atomicOr(&S.removed[k >> 5], 1u << (k & 31));
-          nrem++;
-        }
-      }
-      if (nrem) atomicAdd(&S.misc[4], nrem);
-      __syncthreads();
-      nmatches -= S.misc[4];
-    }
+    if (a.check_ori) nmatches -= rotation_filter<NT>(S.bin, S.sel, nl, S.hist, S.removed, S.misc);
     lap(3);
     if (!(a.retry && nmatches < 20 && attempt == 0)) break;
     th = 2 * a.th;

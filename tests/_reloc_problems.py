@@ -130,6 +130,29 @@ def conflict_problem():
 
 
 @functools.lru_cache(maxsize=1)
+def wide_pitch_problem(seed=31):
+    """conflict_problem() behind 1030 padding keypoints (1090 keypoints, 128
+    keyframe points): more than 1024 keypoints, so the 2048-keypoint build of
+    the matcher runs and every match lies at an index >= 1030. The padding is
+    spread over the image but kept out of the +-40 px box around the points'
+    projection (320, 240), with random octaves, angles and descriptors"""
+    P = conflict_problem()
+    rng = np.random.default_rng(seed)
+    npad = 1030
+    pad = np.zeros(npad, KP)
+    pad["x"] = rng.uniform(0, 640, npad)
+    pad["y"] = rng.uniform(0, 480, npad)
+    box = (np.abs(pad["x"] - 320) < 40) & (np.abs(pad["y"] - 240) < 40)
+    pad["x"][box] += np.where(pad["x"][box] < 320, -80, 80)
+    pad["angle"] = rng.uniform(0, 360, npad)
+    pad["octave"] = rng.integers(0, 8, npad)
+    pdesc = rng.integers(0, 256, (npad, 32), dtype=np.uint8)
+    cur = dict(Tcw=P["cur"]["Tcw"], kps_un=np.concatenate([pad, P["cur"]["kps_un"]]),
+               desc=np.concatenate([pdesc, P["cur"]["desc"]]))
+    return dict(P, cur=cur, cur_has_mp=np.zeros(len(cur["kps_un"]), np.uint8), npad=npad)
+
+
+@functools.lru_cache(maxsize=1)
 def level_edge_problem():
     """points whose predicted level is 0 (mfMaxDistance below the distance) and
     nlevels - 1 (far above it), each with keypoints of every octave around its

@@ -11,7 +11,7 @@ import pytest
 
 import _reloc_ref as R
 from _reloc_problems import (KP, conflict_problem, level_edge_problem, random_db_batch,
-                             sequence_problem, unit_bow)
+                             sequence_problem, unit_bow, wide_pitch_problem)
 
 pytestmark = pytest.mark.gpu
 
@@ -180,6 +180,20 @@ def test_proj_conflict_128_points_40_keypoints(orbpl, check_ori):
     if not check_ori:
         # the first points take the keypoints one by one, best first
         assert n == P["expect_claims"] and sorted(m[m >= 0].tolist()) == list(range(n))
+
+
+@pytest.mark.parametrize("check_ori", [True, False])
+def test_proj_conflict_wide_pitch(orbpl, check_ori):
+    """more than 1024 keypoints: the 2048-keypoint build of the matcher, whose
+    matches all lie behind the padding"""
+    P = wide_pitch_problem()
+    assert len(P["cur"]["kps_un"]) == 1090 and len(P["kf"]["angle"]) == 128
+    m, n = _run_proj(orbpl, P, 10, 100, check_ori)
+    assert (np.flatnonzero(m >= 0) >= 1024).all()
+    if check_ori:
+        assert n >= 1
+    else:
+        assert n == P["expect_claims"]
 
 
 def test_proj_level_edges(orbpl):
