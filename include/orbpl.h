@@ -550,6 +550,155 @@ int orbpnp_iterate_batch_device(const orbpnp_device_batch* b, int nsolvers, int 
                                 void* stream);
 
 /* ------------------------------------------------------------------------
+ * Tracking::Relocalization (Tracking.cc:2049-2269) as one batched call over
+ * many lost frames, each with its own keyframe database:
+ * place recognition, SearchByBoW against every candidate, and then rounds of
+ * PnPsolver::iterate(5), PoseOptimization and the two SearchByProjection
+ * refinements for all candidates of all frames side by side, with the
+ * reference's sequential order restored by an ordered selection per round.
+ * The host reads back one count per round.
+ * ---------------------------------------------------------------------- */
+#define ORBRL_OK 0               /* relocalised: Tcw, assignments, winner are set */
+#define ORBRL_NO_CANDIDATES 1    /* DetectRelocalizationCandidates returned none */
+#define ORBRL_FAILED 2           /* every candidate was discarded */
+#define ORBRL_DRAW_EXHAUSTED 3   /* P31: a solver's next iterate(5) may need more draws than remain */
+/* per-candidate record, int32 each; -1 = stage not reached in the last call */
+#define ORBRL_REC_BOW_MATCHES 0  /* SearchByBoW's return value */
+#define ORBRL_REC_DISCARDED 1    /* vbDiscarded */
+#define ORBRL_REC_CALLS 2        /* iterate() calls */
+#define ORBRL_REC_ITERATIONS 3   /* mnIterations */
+#define ORBRL_REC_DRAWS_USED 4   /* the stream's cursor */
+#define ORBRL_REC_RESULT 5       /* last call: 0 empty, 1 refined, 2 best at exhaustion */
+#define ORBRL_REC_NO_MORE 6
+#define ORBRL_REC_N_INLIERS 7
+#define ORBRL_REC_G1 8           /* nGood after the first PoseOptimization */
+#define ORBRL_REC_NADD1 9        /* SearchByProjection(th 10, ORBdist 100) */
+#define ORBRL_REC_G2 10
+#define ORBRL_REC_NADD2 11       /* SearchByProjection(th 3, ORBdist 64) */
+#define ORBRL_REC_G3 12
+#define ORBRL_REC_INTS 13
+typedef struct orbrl_handle orbrl_handle;
+/* The handle owns SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991)'s table
+ * for N = 0..2048 (orbpnp_ransac_parameters, P28) and the workspace, which
+ * grows with the batch. level_sigma2 = mvLevelSigma2; kp_pitch 1024 or 2048 =
+ * the most keypoints of a frame or a keyframe; draw_pitch = raw rand() values
+ * per candidate stream (P30), a multiple of 4 in [20, 1280]. */
+int orbrl_create(const orbpl_camera* cam, const float* scale_factors, const float* level_sigma2,
+                 int nlevels, int max_problems, int kp_pitch, int draw_pitch, orbrl_handle** out);
+void orbrl_destroy(orbrl_handle* h);
+/* the table's first n_entries rows (host only) */
+int orbrl_ransac_table(int32_t* min_inliers, int32_t* max_its, int n_entries);
+/* One lost frame and its database, host pointers. The database fields are
+ * orbkf_problem's (reloc_score in/out). Keyframe k's features are the entries
+ * kf_feat_off[k] .. kf_feat_off[k + 1] of the concatenated per-feature arrays:
+ * mvKeysUn angle, FeatureVector node id (-1 none), descriptor, kf_valid = the
+ * feature's map point exists (bad ones are absent, P27), and that point's
+ * world position, raw mfMinDistance / mfMaxDistance and descriptor. The
+ * frame: n keypoints (mvKeysUn, mvuRight, descriptors, node ids), its
+ * BowVector, and n_draw_streams streams of draw_pitch raw rand() values:
+ * candidate c draws from stream c (a candidate without a stream is out of
+ * draws at once). Outputs: ok, status (ORBRL_*), winner = database index or
+ * -1, rounds = passes of the reference's while loop begun, Tcw, n_good,
+ * n_candidates = nCandidates at the end, ncand / cand = place recognition's
+ * result, mp_kf_feature[n] = mvpMapPoints as the winner's feature indices (-1
+ * none), outlier[n] = mvbOutlier where a map point is assigned (0 elsewhere),
+ * records[64][ORBRL_REC_INTS]. On failure Tcw is zero, every assignment -1. */
+typedef struct orbrl_problem {
+  int32_t nkf;
+  const int32_t* kf_off;
+  const uint32_t* kf_words;
+  const double* kf_vals;
+  const int32_t* covis;
+  float* reloc_score;
+  const int32_t* kf_feat_off;
+  const float* kf_angle;
+  const int32_t* kf_feat_node;
+  const uint8_t* kf_desc;
+  const uint8_t* kf_valid;
+  const float* mp_xyz;
+  const float* mp_min_dist;
+  const float* mp_max_dist;
+  const uint8_t* mp_desc;
+  int32_t n;
+  const orbpl_keypoint* kps_un;
+  const float* uright;
+  const uint8_t* desc;
+  const int32_t* feat_node;
+  int32_t nq_words;
+  const uint32_t* q_words;
+  const double* q_vals;
+  int32_t n_draw_streams;
+  const int32_t* draws;
+  int32_t ok, status, winner, rounds, n_good, n_candidates, ncand;
+  int32_t cand[64];
+  float Tcw[16];
+  int32_t* mp_kf_feature;
+  uint8_t* outlier;
+  int32_t* records;
+} orbrl_problem;
+/* n <= max_problems problems in one call. ORBPL_ERR_ARG: more than 64
+ * keyframes, more than 4096 words, more keypoints or keyframe features than
+ * kp_pitch, scoring other than L1_NORM = 0. ORBPL_ERR_OVERFLOW: some problem
+ * ended with ORBRL_DRAW_EXHAUSTED (every problem's outputs are still set). */
+int orbrl_relocalize(orbrl_handle* h, orbrl_problem* problems, int n, int scoring);
+/* The same over pitched device arrays on `stream` (a hipStream_t, NULL = the
+ * null stream); orbrl_relocalize packs its problems into this layout and
+ * calls it. The call returns when the batch is decided: it waits for the
+ * stream once before the rounds and once per round, for 4 bytes each time.
+ * Databases as in orbkf_device_batch. Keyframe k of problem p is slot
+ * d_kf_first[p] + k: d_kf_n[slot] features at slot * kp_pitch of the
+ * per-feature arrays. Frame p: d_n[p] keypoints at p * kp_pitch. Draw stream
+ * c of problem p at (p * stream_pitch + c) * draw_pitch, d_n_streams[p] <=
+ * stream_pitch <= 64 of them. Outputs per problem: d_cand 64, d_Tcw 16,
+ * d_mp_kf_feature / d_outlier kp_pitch, d_records 64 x ORBRL_REC_INTS, the
+ * rest one int32. A problem out of draws shows in d_status only. */
+typedef struct orbrl_device_batch {
+  const int32_t* d_nkf;
+  const int32_t* d_kf_off;
+  const uint32_t* d_kf_words;
+  const double* d_kf_vals;
+  int64_t ent_pitch;
+  const int32_t* d_covis;
+  float* d_reloc_score;
+  const int32_t* d_q_n;
+  const uint32_t* d_q_words;
+  const double* d_q_vals;
+  int64_t q_pitch;
+  const int32_t* d_kf_first;
+  const int32_t* d_kf_n;
+  const float* d_kf_angle;
+  const int32_t* d_kf_feat_node;
+  const uint8_t* d_kf_desc;
+  const uint8_t* d_kf_valid;
+  const float* d_mp_xyz;
+  const float* d_mp_min_dist;
+  const float* d_mp_max_dist;
+  const uint8_t* d_mp_desc;
+  const int32_t* d_n;
+  const orbpl_keypoint* d_kps_un;
+  const float* d_uright;
+  const uint8_t* d_desc;
+  const int32_t* d_feat_node;
+  const int32_t* d_draws;
+  const int32_t* d_n_streams;
+  int32_t stream_pitch;
+  int32_t* d_cand;
+  int32_t* d_ncand;
+  int32_t* d_ok;
+  int32_t* d_status;
+  int32_t* d_winner;
+  int32_t* d_rounds;
+  int32_t* d_n_good;
+  int32_t* d_n_candidates;
+  float* d_Tcw;
+  int32_t* d_mp_kf_feature;
+  uint8_t* d_outlier;
+  int32_t* d_records;
+} orbrl_device_batch;
+int orbrl_relocalize_batch_device(orbrl_handle* h, const orbrl_device_batch* b, int n, int scoring,
+                                  void* stream);
+
+/* ------------------------------------------------------------------------
  * Optimizer::PoseOptimization / PoseOptimizationWithLines
  * (Optimizer.cc:375-619, 2132-2486): 4 rounds x 10 Levenberg-Marquardt
  * iterations on one SE3 vertex, Huber kernel in rounds 0-2, chi2 outlier

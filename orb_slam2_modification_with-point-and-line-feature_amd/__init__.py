@@ -1736,3 +1736,231 @@ class PnpDeviceProblems:
                      state=dict(iterations=int(it[s]), best_inliers=int(bi[s]),
                                 best_mask=bm[s, :self.n[s]].copy(), best_Tcw=bT[s].copy()))
                 for s in range(self.ns)]
+
+
+# ---------------------------------------------------------------------------
+# Tracking::Relocalization as one batched call
+# ---------------------------------------------------------------------------
+RL_OK, RL_NO_CANDIDATES, RL_FAILED, RL_DRAW_EXHAUSTED = 0, 1, 2, 3
+RL_REC = ("bow_matches", "discarded", "calls", "iterations", "draws_used", "result", "no_more",
+          "n_inliers", "g1", "nadd1", "g2", "nadd2", "g3")
+RL_TABLE_N = 2048
+
+
+class RelocProblem(C.Structure):
+    _fields_ = ([("nkf", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("kf_off", "kf_words", "kf_vals", "covis", "reloc_score",
+                                           "kf_feat_off", "kf_angle", "kf_feat_node", "kf_desc",
+                                           "kf_valid", "mp_xyz", "mp_min_dist", "mp_max_dist",
+                                           "mp_desc")] +
+                [("n", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("kps_un", "uright", "desc", "feat_node")] +
+                [("nq_words", C.c_int32), ("q_words", C.c_void_p), ("q_vals", C.c_void_p),
+                 ("n_draw_streams", C.c_int32), ("draws", C.c_void_p)] +
+                [(k, C.c_int32) for k in ("ok", "status", "winner", "rounds", "n_good",
+                                          "n_candidates", "ncand")] +
+                [("cand", C.c_int32 * 64), ("Tcw", C.c_float * 16), ("mp_kf_feature", C.c_void_p),
+                 ("outlier", C.c_void_p), ("records", C.c_void_p)])
+
+
+def _declare_reloc(L):
+    vp, i = C.c_void_p, C.c_int
+    L.orbrl_create.argtypes = [vp, vp, vp, i, i, i, i, C.POINTER(vp)]
+    L.orbrl_destroy.argtypes = [vp]
+    L.orbrl_destroy.restype = None
+    L.orbrl_ransac_table.argtypes = [vp, vp, i]
+    L.orbrl_relocalize.argtypes = [vp, vp, i, i]
+
+
+_declare_before_reloc = _declare
+
+
+def _declare(L):  # noqa: F811
+    _declare_before_reloc(L)
+    _declare_reloc(L)
+
+
+def reloc_ransac_table(n_entries=RL_TABLE_N + 1):
+    """SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991)'s (min_inliers,
+    max_its) for N = 0 .. n_entries - 1, as the Relocalizer's handle holds it."""
+    mn = np.zeros(n_entries, np.int32)
+    mx = np.zeros(n_entries, np.int32)
+    check(lib().orbrl_ransac_table(_ptr(mn), _ptr(mx), n_entries), "orbrl_ransac_table")
+    return mn, mx
+
+
+class Relocalizer:
+    """Tracking::Relocalization (Tracking.cc:2049-2269) for a batch of lost
+    frames, each with its own keyframe database. A problem is a dict:
+    ``kf_bows`` / ``covis`` / ``reloc_score`` as for detect_reloc_batch,
+    ``kfs`` = per database keyframe a dict of per-feature arrays (angle,
+    feat_node, desc, valid, mp_xyz, mp_min_dist, mp_max_dist, mp_desc),
+    ``frame`` = dict(kps_un, uright, desc, feat_node, bow_words, bow_vals) and
+    ``draws`` = int32 [streams, draw_pitch] raw rand() values, stream c for
+    candidate c (P30)."""
+
+    def __init__(self, camera, scale_factors, level_sigma2, max_problems=64, kp_pitch=1024,
+                 draw_pitch=4 * PNP_MAX_ITERATIONS):
+        sf, s2 = _c(scale_factors, np.float32), _c(level_sigma2, np.float32)
+        self._h = C.c_void_p()
+        self.kp_pitch, self.draw_pitch, self.max_problems = kp_pitch, draw_pitch, max_problems
+        check(lib().orbrl_create(C.byref(camera), _ptr(sf), _ptr(s2), len(sf), int(max_problems),
+                                 int(kp_pitch), int(draw_pitch), C.byref(self._h)), "orbrl_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().orbrl_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def relocalize_batch(self, problems, scoring=0):
+        """Returns per problem a dict: ok, status (RL_*), winner (database
+        index or -1), rounds, Tcw [4, 4], n_good, n_candidates, cand,
+        mp_kf_feature [n], outlier [n], records (one dict of RL_REC per
+        candidate), reloc_score (updated copy). Raises OrbplError
+        (ORBPL_ERR_OVERFLOW) when a problem runs out of draws (P31); the
+        results up to there are in the exception's ``results``."""
+        nq = len(problems)
+        arr = (RelocProblem * max(1, nq))()
+        keep, outs = [], []
+        for p, pr in enumerate(problems):
+            bows, kfs, F = pr["kf_bows"], pr["kfs"], pr["frame"]
+            nkf = len(bows)
+            assert len(kfs) == nkf
+            off = np.zeros(nkf + 1, np.int32)
+            foff = np.zeros(nkf + 1, np.int32)
+            for k in range(nkf):
+                off[k + 1] = off[k] + len(bows[k][0])
+                foff[k + 1] = foff[k] + len(kfs[k]["angle"])
+
+            def cat(key, dt, shape):
+                if not nkf:
+                    return np.zeros((0,) + shape, dt)
+                return _c(np.concatenate([_c(kf[key], dt).reshape((-1,) + shape) for kf in kfs]), dt)
+
+            kw = (_c(np.concatenate([_c(w, np.uint32) for w, _ in bows]), np.uint32) if nkf
+                  else np.zeros(0, np.uint32))
+            kv = (_c(np.concatenate([_c(v, np.float64) for _, v in bows]), np.float64) if nkf
+                  else np.zeros(0, np.float64))
+            cov = np.full((max(1, nkf), KFDB_COVISIBLES), -1, np.int32)
+            for k, lst in enumerate(pr.get("covis", [])[:nkf]):
+                lst = list(lst)[:KFDB_COVISIBLES]
+                cov[k, :len(lst)] = lst
+            rs = np.zeros(max(1, nkf), np.float32)
+            if pr.get("reloc_score") is not None:
+                rs[:nkf] = _c(pr["reloc_score"], np.float32)
+            ka, kn = cat("angle", np.float32, ()), cat("feat_node", np.int32, ())
+            kd, kvl = cat("desc", np.uint8, (32,)), cat("valid", np.uint8, ())
+            mx, mmin = cat("mp_xyz", np.float32, (3,)), cat("mp_min_dist", np.float32, ())
+            mmax, md = cat("mp_max_dist", np.float32, ()), cat("mp_desc", np.uint8, (32,))
+            kps, ur = _c(F["kps_un"], KP_DTYPE), _c(F["uright"], np.float32)
+            fd, fn = _c(F["desc"], np.uint8), _c(F["feat_node"], np.int32)
+            qw, qv = _c(F["bow_words"], np.uint32), _c(F["bow_vals"], np.float64)
+            dr = _c(pr["draws"], np.int32).reshape(-1, self.draw_pitch)
+            n = len(kps)
+            om = np.full(max(1, n), -1, np.int32)
+            oo = np.zeros(max(1, n), np.uint8)
+            rec = np.zeros((64, len(RL_REC)), np.int32)
+            keep += [off, foff, kw, kv, cov, rs, ka, kn, kd, kvl, mx, mmin, mmax, md, kps, ur, fd,
+                     fn, qw, qv, dr, om, oo, rec]
+            r = arr[p]
+            r.nkf = nkf
+            for name, a in (("kf_off", off), ("kf_words", kw), ("kf_vals", kv), ("covis", cov),
+                            ("reloc_score", rs), ("kf_feat_off", foff), ("kf_angle", ka),
+                            ("kf_feat_node", kn), ("kf_desc", kd), ("kf_valid", kvl),
+                            ("mp_xyz", mx), ("mp_min_dist", mmin), ("mp_max_dist", mmax),
+                            ("mp_desc", md), ("kps_un", kps), ("uright", ur), ("desc", fd),
+                            ("feat_node", fn), ("q_words", qw), ("q_vals", qv), ("draws", dr),
+                            ("mp_kf_feature", om), ("outlier", oo), ("records", rec)):
+                setattr(r, name, a.ctypes.data if a.size else None)
+            r.mp_kf_feature, r.outlier = om.ctypes.data, oo.ctypes.data
+            r.n, r.nq_words, r.n_draw_streams = n, len(qw), len(dr)
+            outs.append((nkf, n, om, oo, rec, rs))
+        rc = lib().orbrl_relocalize(self._h, C.byref(arr), nq, int(scoring))
+        if rc not in (0, -5):
+            check(rc, "orbrl_relocalize")
+        res = []
+        for p, (nkf, n, om, oo, rec, rs) in enumerate(outs):
+            r = arr[p]
+            nc = r.ncand
+            res.append(dict(ok=bool(r.ok), status=r.status, winner=r.winner, rounds=r.rounds,
+                            Tcw=np.array(r.Tcw, np.float32).reshape(4, 4), n_good=r.n_good,
+                            n_candidates=r.n_candidates, cand=np.array(r.cand[:nc], np.int32),
+                            mp_kf_feature=om[:n].copy(), outlier=oo[:n].copy(),
+                            records=[dict(zip(RL_REC, (int(v) for v in rec[c])))
+                                     for c in range(nc)],
+                            reloc_score=rs[:nkf].copy()))
+        if rc == -5:
+            try:
+                check(rc, "orbrl_relocalize")
+            except OrbplError as e:
+                e.results = res
+                raise
+        return res
+
+    def relocalize(self, voc, problem, levelsup=4):
+        """One lost frame: Frame::ComputeBoW through ``voc`` (an ORBVocabulary)
+        for ``problem["frame"]`` (its feat_node / bow_words / bow_vals are
+        filled in), then relocalize_batch. The draws come from the C library's
+        rand() (pnp_srand), draw_pitch values per candidate in candidate order;
+        values a candidate does not consume are dropped (P30). A convenience:
+        to know how many streams to draw it runs place recognition once on its
+        own (detect_reloc_batch) before the call runs it again - a launch and
+        a host round trip that relocalize_batch with the caller's own streams
+        does not have."""
+        F = dict(problem["frame"])
+        bw, bv, fn = voc.transform(F["desc"], levelsup)[:3]
+        F.update(bow_words=bw, bow_vals=bv, feat_node=fn)
+        pre = detect_reloc_batch([dict(kf_bows=problem["kf_bows"], covis=problem.get("covis", []),
+                                       reloc_score=problem.get("reloc_score"), q_words=bw,
+                                       q_vals=bv)])[0]
+        nc = len(pre["cand"])
+        draws = np.zeros((nc, self.draw_pitch), np.int32)
+        for c in range(nc):
+            draws[c] = _pnp_take_rand(self.draw_pitch)
+            del _pnp_rand_queue[:self.draw_pitch]
+        return self.relocalize_batch([dict(problem, frame=F, draws=draws)])[0]
+
+
+class RelocDeviceBatch(C.Structure):
+    """orbrl_device_batch: pitched device arrays (see include/orbpl.h)"""
+    _fields_ = ([(k, C.c_void_p) for k in ("d_nkf", "d_kf_off", "d_kf_words", "d_kf_vals")] +
+                [("ent_pitch", C.c_int64), ("d_covis", C.c_void_p), ("d_reloc_score", C.c_void_p),
+                 ("d_q_n", C.c_void_p), ("d_q_words", C.c_void_p), ("d_q_vals", C.c_void_p),
+                 ("q_pitch", C.c_int64)] +
+                [(k, C.c_void_p) for k in ("d_kf_first", "d_kf_n", "d_kf_angle", "d_kf_feat_node",
+                                           "d_kf_desc", "d_kf_valid", "d_mp_xyz", "d_mp_min_dist",
+                                           "d_mp_max_dist", "d_mp_desc", "d_n", "d_kps_un",
+                                           "d_uright", "d_desc", "d_feat_node", "d_draws",
+                                           "d_n_streams")] +
+                [("stream_pitch", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("d_cand", "d_ncand", "d_ok", "d_status", "d_winner",
+                                           "d_rounds", "d_n_good", "d_n_candidates", "d_Tcw",
+                                           "d_mp_kf_feature", "d_outlier", "d_records")])
+
+
+def _declare_reloc_device(L):
+    L.orbrl_relocalize_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_void_p]
+
+
+_declare_before_reloc_device = _declare
+
+
+def _declare(L):  # noqa: F811
+    _declare_before_reloc_device(L)
+    _declare_reloc_device(L)
+
+
+def _reloc_relocalize_batch_device(self, batch, n, scoring=0, stream=None):
+    """orbrl_relocalize_batch_device over a RelocDeviceBatch of n problems"""
+    check(lib().orbrl_relocalize_batch_device(self._h, C.byref(batch), int(n), int(scoring),
+                                              stream), "orbrl_relocalize_batch_device")
+
+
+Relocalizer.relocalize_batch_device = _reloc_relocalize_batch_device

@@ -1061,4 +1061,49 @@ void launch_match_kf(const TrackConsts& c, const MatchKfArgs& a, int batch, hipS
   }
 }
 
+// ---------------------------------------------------------------------------
+// Tracking::Relocalization's ORBmatcher(0.75, true).SearchByBoW(pKF,
+// mCurrentFrame, vvpMapPointMatches[i]) (Tracking.cc:2094) for every pair
+// (lost frame p, candidate c) of a batch: one workgroup per pair, the
+// candidate keyframe's FeatureVector / descriptors / angles / map point flags
+// against frame p's. Descriptors stay in global memory (L2), as in k_trk_bow.
+// ---------------------------------------------------------------------------
+template <int CAP>
+__global__ void __launch_bounds__(256) k_reloc_bow(RelocDev d) {
+  __shared__ BowShared<CAP> B;
+  const int q = blockIdx.x, p = q / d.C, c = q - p * d.C;
+  if (c >= d.ncand[p]) {
+    if (threadIdx.x == 0) d.bow_nm[q] = 0;
+    return;
+  }
+  const long long fb = (long long)p * d.kp_pitch;
+  const long long kb = (long long)(d.kf_first[p] + d.cand[p * kKfdbMaxKf + c]) * d.kp_pitch;
+  BowArgs b;
+  b.nkf = min(max(d.kf_n[kb / d.kp_pitch], 0), d.kp_pitch);
+  b.kf_node = d.kf_feat_node + kb;
+  b.kf_valid = d.kf_valid + kb;
+  b.kf_desc = d.kf_desc + kb * 32;
+  b.kf_angle = d.kf_angle + kb;
+  b.kf_angle_stride = 1;
+  b.nf = min(max(d.n[p], 0), d.kp_pitch);
+  b.f_node = d.feat_node + fb;
+  b.f_desc = d.desc + fb * 32;
+  b.f_angle = &d.kps_un[fb].angle;
+  b.f_angle_stride = (int)(sizeof(KeyPointD) / sizeof(float));
+  b.nnratio = 0.75f;
+  b.check_ori = 1;
+  b.match = d.bow_match + (long long)q * d.kp_pitch;
+  b.nmatches = d.bow_nm + q;
+  match_bow_body<CAP, 256>(b, B, nullptr);
+}
+
+void launch_reloc_bow(const RelocDev& d, hipStream_t s) {
+  const int grid = d.np * d.C;
+  if (grid <= 0) return;
+  if (d.kp_pitch <= 1024)
+    hipLaunchKernelGGL(k_reloc_bow<1024>, dim3(grid), dim3(256), 0, s, d);
+  else
+    hipLaunchKernelGGL(k_reloc_bow<kBowMax>, dim3(grid), dim3(256), 0, s, d);
+}
+
 }  // namespace orbpl

@@ -139,8 +139,11 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_iterate(PnpArgs a) {
     return;
   }
   long long want = std::max((long long)max_its - it0, (long long)a.n_iterations);
-  const int H = (int)std::min(std::max(want, 0LL), (long long)std::min(kPnpMaxIts, a.draw_pitch / 4));
-  const int* draws = a.draws + (long long)s * a.draw_pitch;
+  // (a caller that keeps a cursor into the solver's draws passes it as draw_off)
+  const int doff = a.draw_off ? min(max(a.draw_off[s], 0), a.draw_pitch) : 0;
+  const int H = (int)std::min(std::max(want, 0LL),
+                              (long long)std::min(kPnpMaxIts, (a.draw_pitch - doff) / 4));
+  const int* draws = a.draws + (long long)s * a.draw_pitch + doff;
 
   for (int i = tid; i < N; i += kPnpThreads) sh.best[i] = st_best[i];
   if (tid < 16) sh.best_Tcw[tid] = a.best_Tcw[16 * s + tid];

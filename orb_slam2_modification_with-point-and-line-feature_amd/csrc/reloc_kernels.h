@@ -99,7 +99,136 @@ struct PnpArgs {
   int* n_inliers;
   uint8_t* inliers;            // pt_pitch per solver
   int* draws_consumed;
+  const int* draw_off = nullptr;  // optional: solver s reads its draws from draws[s] + draw_off[s]
+                                  // (and runs at most (draw_pitch - draw_off[s]) / 4 hypotheses)
 };
 void launch_pnp_iterate(const PnpArgs& a, int nsolvers, hipStream_t s);
+
+//   launch_reloc_* : Tracking::Relocalization itself (Tracking.cc:2049-2269,
+//                    DESIGN.md P30-P32), reloc.hip. The unit of work is a pair
+//                    q = p * C + c: problem (lost frame) p, candidate slot c < C,
+//                    C = the largest candidate count of the batch.
+constexpr int kRelocRec = 13;   // ints per candidate record (ORBRL_REC_*)
+enum { kRecBow, kRecDisc, kRecCalls, kRecIts, kRecDraws, kRecResult, kRecNoMore, kRecInl,
+       kRecG1, kRecAdd1, kRecG2, kRecAdd2, kRecG3 };
+constexpr int kRelocTableN = 2048;   // SetRansacParameters table: N = 0 .. 2048
+
+struct RelocDev {
+  int np, C, kp_pitch, draw_pitch, stream_pitch;
+  // ---- inputs: the lost frames, problem p at p * kp_pitch ----
+  const int* n;
+  const KeyPointD* kps_un;
+  const float* uright;
+  const uint8_t* desc;
+  const int* feat_node;
+  // the databases' keyframes: keyframe k of problem p is slot kf_first[p] + k,
+  // its feature arrays at slot * kp_pitch
+  const int* kf_first;
+  const int* kf_n;
+  const float* kf_angle;
+  const int* kf_feat_node;
+  const uint8_t* kf_desc;
+  const uint8_t* kf_valid;
+  const float* mp_xyz;
+  const float* mp_min_dist;
+  const float* mp_max_dist;
+  const uint8_t* mp_desc;
+  // P30: stream c of problem p at (p * stream_pitch + c) * draw_pitch
+  const int* draws;
+  const int* n_streams;
+  // place recognition's result (k_kfdb_reloc)
+  const int* cand;     // kKfdbMaxKf per problem
+  const int* ncand;
+  // constants
+  const int* table;    // [kRelocTableN + 1][2]: min_inliers, max_its
+  float sigma2[kMaxLevelsT];
+  float cam[4];
+  // ---- per pair, arrays at q * kp_pitch ----
+  int* bow_match;
+  int* bow_nm;
+  float* p2d;
+  float* p3d;
+  float* max_error;
+  int* kp_index;
+  int* n_corr;
+  int* n_run;          // n_corr where the pair runs this round, else 0
+  int* min_inl;
+  int* max_its;
+  float* pcam;
+  int* pdraws;         // q * draw_pitch
+  int* avail;          // draws of the pair's stream (0: the problem has no stream c)
+  int* cursor;
+  int* iterations;
+  int* best_count;
+  uint8_t* best_mask;
+  float* best_Tcw;
+  float* pnp_Tcw;
+  int* result;
+  int* no_more;
+  int* n_inliers;
+  uint8_t* inliers;
+  int* consumed;
+  // the candidate's copy of the frame and of its keyframe (k_pose, k_match_kf)
+  int* pn;
+  KeyPointD* pkps;
+  float* puright;
+  uint8_t* pdesc;
+  int* pkf_n;
+  float* pkf_angle;
+  uint8_t* pkf_valid;
+  float* pmp_xyz;
+  float* pmp_min;
+  float* pmp_max;
+  uint8_t* pmp_desc;
+  // the candidate's view of mCurrentFrame
+  int* match;          // mvpMapPoints as keyframe feature indices
+  uint8_t* has_mp;
+  uint8_t* outlier;
+  uint8_t* kf_found;   // sFound
+  float* Tcw;
+  int* ninl;           // k_pose's count
+  int* add_match;      // k_match_kf's output
+  int* add_n;
+  int* mk_cur_n;       // counts k_match_kf sees: 0 unless the pair searches
+  int* mk_kf_n;
+  // director state
+  uint8_t* run;
+  uint8_t* live;       // committed !vbDiscarded
+  uint8_t* live_w;
+  uint8_t* win;
+  int* stage;
+  int* want;           // the pair is in the next launch_pose
+  int* ngood;
+  int* rec_w;          // kRelocRec per pair
+  int* list;
+  int* list_n;
+  int* exh_at;         // per problem: first candidate out of draws (64: none)
+  int* done;
+  int* undecided;
+  int* maxc;
+  // ---- outputs per problem ----
+  int* ok;
+  int* status;
+  int* winner;
+  int* rounds;
+  int* n_good;
+  int* n_live;
+  float* out_Tcw;
+  int* out_match;      // kp_pitch per problem
+  uint8_t* out_outlier;
+  int* rec;            // kKfdbMaxKf x kRelocRec per problem
+};
+void launch_reloc_bow(const RelocDev& d, hipStream_t s);       // match_local.hip
+void launch_reloc_init(const RelocDev& d, hipStream_t s);      // outputs cleared, maxc
+void launch_reloc_setup(const RelocDev& d, hipStream_t s);
+void launch_reloc_begin(const RelocDev& d, hipStream_t s);
+void launch_reloc_after_pnp(const RelocDev& d, hipStream_t s);
+void launch_reloc_stage(const RelocDev& d, int phase, hipStream_t s);   // then the pose list
+void launch_reloc_select(const RelocDev& d, hipStream_t s);
+
+// Frame constants for the relocalisation call (track_runtime.cpp's make_consts;
+// cam is an orbpl_camera)
+int reloc_consts(const void* cam, const float* scale, const float* inv_sigma2, int nlevels,
+                 TrackConsts* out, float* log_scale);
 
 }  // namespace orbpl

@@ -110,6 +110,15 @@ hipStream_t scratch_stream() { return nullptr; }  // host-pointer APIs use the n
 
 }  // namespace
 
+int orbpl::reloc_consts(const void* cam, const float* scale, const float* inv_sigma2, int nlevels,
+                        TrackConsts* out, float* log_scale) {
+  const int rc = make_consts(static_cast<const orbpl_camera*>(cam), scale, inv_sigma2, nlevels, out);
+  if (rc) return rc;
+  // Frame::mfLogScaleFactor (P15), as orbm_search_by_projection_kf takes it
+  *log_scale = nlevels > 1 ? (float)lsdm::log_((double)scale[1]) : 1.0f;
+  return ORBPL_OK;
+}
+
 bool orbpl::lsd_split_decision(int n_streams) {
   return split_on("ORBPL_LSD_SPLIT", n_streams, kLsdSplitMin);
 }

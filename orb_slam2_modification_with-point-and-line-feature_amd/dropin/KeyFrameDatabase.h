@@ -27,6 +27,11 @@ class KeyFrameDatabase {
   // shares a word with F and mRelocScore of every scored one, as the reference
   // does; mRelocScore starts at 0.0f and persists
   std::vector<KeyFrame*> DetectRelocalizationCandidates(Frame* F);
+  // the keyframes in add() order (Tracking::Relocalization packs them)
+  std::vector<KeyFrame*> GetKeyFrames() {
+    std::unique_lock<std::mutex> lock(mMutex);
+    return mvKeyFrames;
+  }
 
  protected:
   const ORBVocabulary* mpVoc;

@@ -37,6 +37,9 @@
 //   KeyFrameDatabase::DetectRelocalizationCandidates(&F); formats at reloc_mode()
 //   dropin_driver --pnp <in.bin> <out.bin>: one ORB_SLAM2::PnPsolver on a dumped
 //   problem, iterate(n) repeated until a pose or bNoMore; formats at pnp_mode()
+//   dropin_driver --relocalize <in.bin> <out.bin>: Tracking::Relocalization on a
+//   dumped lost frame and database through the drop-in Tracking class, under
+//   srand(seed); formats at relocalize_mode()
 //   dropin_driver --fail: a Frame from an 8x8 image, which the library's
 //   extractors reject: the error must reach the caller as an exception (the
 //   line thread joined first), printed as "caught: <message>", exit 0
@@ -78,6 +81,7 @@
 #include "ORBmatcher.h"
 #include "Optimizer.h"
 #include "PnPsolver.h"
+#include "Tracking.h"
 
 using namespace ORB_SLAM2;
 
@@ -593,6 +597,154 @@ static int pnp_mode(const char* inp, const char* outp) {
   return 0;
 }
 
+// --relocalize in.bin out.bin: Tracking::Relocalization (Tracking.cc:2049-2269)
+// through the drop-in Tracking class, under srand(seed).
+// in.bin : int32 W, H; float fx fy cx cy k1 k2 p1 p2 k3 bf mThDepth; int32
+//          nlevels; float scale[nlevels], levelSigma2[nlevels]; int32 seed,
+//          drawPitch;
+//          frame: int32 N; keysUn (N x 28 B); float uRight[N]; desc (N x 32);
+//          int32 node[N] (-1 none); int32 Q; u32 qwords[Q]; f64 qvals[Q];
+//          int32 K; per keyframe: int32 M; float angle[M]; int32 node[M]; desc
+//          (M x 32); u8 valid[M]; float xyz[3M], minDist[M], maxDist[M]; u8
+//          mpDesc[32M]; int32 B; u32 words[B]; f64 vals[B]; int32 covis[10]
+//          (-1 none); float relocScore
+// out.bin: int32 ok, status, winner (database index, -1), rounds, nGood,
+//          mnLastRelocFrameId; float Tcw[16] (zero when not ok); int32
+//          match[N] (feature of the winner holding mvpMapPoints[i], -1); u8
+//          outlier[N]; int32 ncand; int32 cand[ncand]; int32 records[ncand x
+//          13]; float mRelocScore[K]
+static int relocalize_mode(const char* inp, const char* outp) {
+  FILE* in = fopen(inp, "rb");
+  if (!in) throw std::runtime_error("cannot open input");
+  int32_t wh[2], nlev, sp[2];
+  float camv[11];
+  rd(in, wh, 2);
+  rd(in, camv, 11);
+  rd(in, &nlev, 1);
+  std::vector<float> scale(nlev), sigma2(nlev);
+  rd(in, scale.data(), nlev);
+  rd(in, sigma2.data(), nlev);
+  rd(in, sp, 2);
+  ORBVocabulary voc;
+  KeyFrameDatabase db(voc);
+  Tracking tracker(&voc, &db, sp[1]);
+  Frame& F = tracker.mCurrentFrame;
+  Frame::fx = camv[0]; Frame::fy = camv[1]; Frame::cx = camv[2]; Frame::cy = camv[3];
+  F.mDistCoef.create(1, 5, cv::CV_32F);
+  for (int k = 0; k < 5; k++) F.mDistCoef.at<float>(0, k) = camv[4 + k];
+  F.mbf = camv[9];
+  F.mThDepth = camv[10];
+  F.mnWidth = wh[0];
+  F.mnHeight = wh[1];
+  F.mnScaleLevels = nlev;
+  F.mvScaleFactors = scale;
+  F.mvLevelSigma2 = sigma2;
+  F.mnId = 4321;
+  int32_t N, Q, K;
+  rd(in, &N, 1);
+  F.N = N;
+  F.mvKeysUn.resize(N);
+  rd(in, F.mvKeysUn.data(), N);
+  F.mvuRight.resize(N);
+  rd(in, F.mvuRight.data(), N);
+  F.mDescriptors.create(N > 0 ? N : 1, 32, cv::CV_8U);
+  rd(in, F.mDescriptors.data, (size_t)N * 32);
+  std::vector<int32_t> node(N);
+  rd(in, node.data(), N);
+  for (int i = 0; i < N; i++)
+    if (node[i] >= 0) F.mFeatVec[(DBoW2::NodeId)node[i]].push_back((unsigned)i);
+  rd(in, &Q, 1);
+  std::vector<uint32_t> qw(Q);
+  std::vector<double> qv(Q);
+  rd(in, qw.data(), Q);
+  rd(in, qv.data(), Q);
+  for (int e = 0; e < Q; e++) F.mBowVec[qw[e]] = qv[e];
+  F.mvpMapPoints.assign(N, nullptr);
+  F.mvbOutlier.assign(N, false);
+  rd(in, &K, 1);
+  std::vector<std::unique_ptr<MapPoint>> mps;
+  std::vector<std::unique_ptr<KeyFrame>> kfs;
+  std::vector<std::map<const MapPoint*, int>> mp_index(K);
+  std::map<const KeyFrame*, int> kf_index;
+  std::vector<std::vector<int32_t>> covis(K, std::vector<int32_t>(10));
+  const float zero3[3] = {0, 0, 0};
+  for (int k = 0; k < K; k++) {
+    int32_t M, B;
+    rd(in, &M, 1);
+    std::vector<float> angle(M), xyz(3 * (size_t)M), dmin(M), dmax(M);
+    std::vector<int32_t> knode(M);
+    std::vector<uint8_t> valid(M), mpd(32 * (size_t)M);
+    Frame FK;
+    FK.N = M;
+    FK.mvKeysUn.resize(M);
+    FK.mDescriptors.create(M > 0 ? M : 1, 32, cv::CV_8U);
+    rd(in, angle.data(), M);
+    rd(in, knode.data(), M);
+    rd(in, FK.mDescriptors.data, (size_t)M * 32);
+    rd(in, valid.data(), M);
+    rd(in, xyz.data(), 3 * (size_t)M);
+    rd(in, dmin.data(), M);
+    rd(in, dmax.data(), M);
+    rd(in, mpd.data(), 32 * (size_t)M);
+    FK.mvpMapPoints.assign(M, nullptr);
+    for (int j = 0; j < M; j++) {
+      FK.mvKeysUn[j].angle = angle[j];
+      if (knode[j] >= 0) FK.mFeatVec[(DBoW2::NodeId)knode[j]].push_back((unsigned)j);
+      if (!valid[j]) continue;
+      mps.emplace_back(new MapPoint(&xyz[3 * (size_t)j], &mpd[32 * (size_t)j]));
+      mps.back()->SetNormalAndDistances(zero3, dmin[j], dmax[j]);
+      FK.mvpMapPoints[j] = mps.back().get();
+      mp_index[k][mps.back().get()] = j;
+    }
+    rd(in, &B, 1);
+    std::vector<uint32_t> w(B);
+    std::vector<double> v(B);
+    rd(in, w.data(), B);
+    rd(in, v.data(), B);
+    for (int e = 0; e < B; e++) FK.mBowVec[w[e]] = v[e];
+    rd(in, covis[k].data(), 10);
+    float rs;
+    rd(in, &rs, 1);
+    kfs.emplace_back(new KeyFrame(FK));
+    kfs.back()->mRelocScore = rs;
+    kf_index[kfs.back().get()] = k;
+  }
+  fclose(in);
+  for (int k = 0; k < K; k++) {
+    std::vector<KeyFrame*> ordered;
+    for (int c = 0; c < 10; c++)
+      if (covis[k][c] >= 0) ordered.push_back(kfs[covis[k][c]].get());
+    kfs[k]->SetOrderedCovisibles(ordered);
+    db.add(kfs[k].get());
+  }
+  srand((unsigned)sp[0]);
+  const bool ok = tracker.Relocalization();
+  FILE* o = fopen(outp, "wb");
+  if (!o) throw std::runtime_error("cannot open output");
+  const int winner = ok ? kf_index.at(tracker.mpRelocKF) : -1;
+  wr1<int32_t>(o, ok ? 1 : 0);
+  wr1<int32_t>(o, tracker.mnRelocStatus);
+  wr1<int32_t>(o, winner);
+  wr1<int32_t>(o, tracker.mnRelocRounds);
+  wr1<int32_t>(o, tracker.mnRelocGood);
+  wr1<int32_t>(o, (int32_t)tracker.mnLastRelocFrameId);
+  for (int r = 0; r < 4; r++)
+    for (int c = 0; c < 4; c++) wr1<float>(o, ok ? F.mTcw.at<float>(r, c) : 0.0f);
+  for (int i = 0; i < N; i++) {
+    const MapPoint* p = F.mvpMapPoints[i];
+    wr1<int32_t>(o, p ? mp_index[winner].at(p) : -1);
+  }
+  for (int i = 0; i < N; i++) wr1<uint8_t>(o, F.mvbOutlier[i] ? 1 : 0);
+  wr1<int32_t>(o, (int32_t)tracker.mvpRelocCandidates.size());
+  for (KeyFrame* c : tracker.mvpRelocCandidates) wr1<int32_t>(o, kf_index.at(c));
+  wr(o, tracker.mvRelocRecords.data(), tracker.mvRelocRecords.size());
+  for (int k = 0; k < K; k++) wr1<float>(o, kfs[k]->mRelocScore);
+  fclose(o);
+  printf("dropin_driver --relocalize: %s, status %d, %d rounds\n", ok ? "relocalised" : "lost",
+         tracker.mnRelocStatus, tracker.mnRelocRounds);
+  return 0;
+}
+
 static int fail_mode() {
   ORBextractor ex(1000, 1.2f, 8, 20, 7);
   cv::Mat K = cv::Mat::eye(3, 3, cv::CV_32F);
@@ -641,6 +793,14 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  if (argc == 4 && std::string(argv[1]) == "--relocalize") {
+    try {
+      return relocalize_mode(argv[2], argv[3]);
+    } catch (const std::exception& e) {
+      fprintf(stderr, "dropin_driver: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc == 4 && std::string(argv[1]) == "--stereo") {
     try {
       return stereo_mode(argv[2], argv[3]);
@@ -652,7 +812,8 @@ int main(int argc, char** argv) {
   const bool timing = argc == 4 && std::string(argv[1]) == "--time";
   if (argc != 3 && !timing) {
     fprintf(stderr, "usage: dropin_driver in.bin out.bin | dropin_driver --time in.bin K | "
-                    "dropin_driver --reloc in.bin out.bin | dropin_driver --pnp in.bin out.bin\n");
+                    "dropin_driver --reloc in.bin out.bin | dropin_driver --pnp in.bin out.bin | "
+                    "dropin_driver --relocalize in.bin out.bin\n");
     return 2;
   }
   try {
