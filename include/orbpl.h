@@ -699,6 +699,149 @@ int orbrl_relocalize_batch_device(orbrl_handle* h, const orbrl_device_batch* b, 
                                   void* stream);
 
 /* ------------------------------------------------------------------------
+ * LocalMapping::CreateNewMapPoints() then CreateNewMapLines()
+ * (LocalMapping.cc:346-665, 668-916) with ORBmatcher(0.6,
+ * false).SearchForTriangulation (ORBmatcher.cc:884-1095), ComputeF12
+ * (:1106-1127) and LineMatcher::SearchForTriangulation
+ * (LineMatcher.cpp:1174-1204), non-monocular (nn = 10), for many independent
+ * (current keyframe, <= 10 covisible neighbours) problems in one launch
+ * (DESIGN.md P33-P39). Not called by orbpl_tracker_step (P23 stays).
+ * ---------------------------------------------------------------------- */
+#define ORBLM_MAX_KEYPOINTS 2048   /* per keyframe */
+#define ORBLM_MAX_LINES 256        /* per keyframe */
+#define ORBLM_MAX_NEIGHBOURS 10    /* GetBestCovisibilityKeyFrames(10) */
+/* A keyframe as the block reads it: mnId (observation order, P24), Tcw (16
+ * floats, row-major), n features: mvKeys (UnprojectStereo reads the raw
+ * keypoint), mvKeysUn, mvuRight, mvDepth, descriptors (32 B rows), the
+ * FeatureVector as one node id per feature (orbm_search_by_bow's encoding: -1
+ * none, ids < 2^21 - 1), has_mp = the feature holds a map point and mp_xyz
+ * that point's world position (3 floats per feature, read where has_mp);
+ * nl lines: mvKeyLines (raw), LBD rows (32 B) and mvKeyLineCoefficient (3
+ * doubles per line). */
+typedef struct orblm_keyframe {
+  int32_t id;
+  const float* Tcw;
+  int32_t n;
+  const orbpl_keypoint* kps;
+  const orbpl_keypoint* kps_un;
+  const float* uright;
+  const float* depth;
+  const uint8_t* desc;
+  const int32_t* feat_node;
+  const uint8_t* has_mp;
+  const float* mp_xyz;
+  int32_t nl;
+  const orbpl_keyline* klines;
+  const uint8_t* ldesc;
+  const double* lcoef;
+} orblm_keyframe;
+/* A created map point (48 bytes), in the order of creation: by neighbour,
+ * then by KF1 feature index. desc_from: 0 = KF1's descriptor, 1 = the
+ * neighbour's (ComputeDistinctiveDescriptors with two observations: the
+ * lower-id keyframe's). normal, min_dist, max_dist: UpdateNormalAndDepth with
+ * KF1 as the reference keyframe (P25). */
+typedef struct orblm_point_record {
+  int32_t neighbour, idx1, idx2, desc_from;
+  float xyz[3];
+  float normal[3];
+  float min_dist, max_dist;
+} orblm_point_record;
+/* A created map line (48 bytes), by neighbour, then by KF1 line index: the
+ * end points and, as the map model stores a map line, its descriptor's
+ * source (desc_from as above) with Observations() = 2. */
+typedef struct orblm_line_record {
+  int32_t neighbour, idx1, idx2, desc_from;
+  float xyz6[6];
+  int32_t reserved[2];
+} orblm_line_record;
+/* One problem, host pointers. neigh: n_neigh <= 10 distinct keyframes in
+ * GetBestCovisibilityKeyFrames order. Outputs: points[cur.n] (the first
+ * n_points are set), kf1_point_record[cur.n] = the record that occupies
+ * KF1's feature (-1 none), pairs[10] = SearchForTriangulation's pairs per
+ * neighbour (-1: the neighbour was skipped for its baseline, or is absent);
+ * lines[10 * cur.nl] (n_lines set), kf1_line_record[cur.nl] = the last record
+ * created for KF1's line (AddMapLine overwrites; every record is kept),
+ * line_pairs[10] = LineMatcher::SearchForTriangulation's pairs (-1 as above;
+ * 0 also where the neighbour holds no map point, P39). */
+typedef struct orblm_problem {
+  orblm_keyframe cur;
+  int32_t n_neigh;
+  const orblm_keyframe* neigh;
+  orblm_point_record* points;
+  int32_t n_points;
+  int32_t* kf1_point_record;
+  int32_t pairs[ORBLM_MAX_NEIGHBOURS];
+  orblm_line_record* lines;
+  int32_t n_lines;
+  int32_t* kf1_line_record;
+  int32_t line_pairs[ORBLM_MAX_NEIGHBOURS];
+} orblm_problem;
+/* ORBPL_ERR_ARG: more than 2048 features or 256 lines in a keyframe, more
+ * than 10 neighbours, an octave outside [0, nlevels), a node id >= 2^21 - 1,
+ * nlevels outside [2, 16] (mfScaleFactor = scale_factors[1]), NULL arrays. */
+int orblm_create_new_map_features(const orbpl_camera* cam, const float* scale_factors,
+                                  const float* level_sigma2, int nlevels, orblm_problem* problems,
+                                  int n);
+/* The same over a pitched pool of nkf keyframes in device memory (keyframe k's
+ * features at k * kp_pitch, its lines at k * line_pitch of the per-feature /
+ * per-line arrays, d_kf_Tcw 16 floats each). Problem p: current keyframe
+ * d_cur[p], neighbours d_neigh[p * 10 ..] (-1 = none; the list ends at the
+ * first -1). Outputs per problem: d_points[p * kp_pitch ..], d_n_points[p],
+ * d_kf1_point_record[p * kp_pitch ..], d_pairs[p * 10 ..], d_lines[p * 10 *
+ * line_pitch ..], d_n_lines[p], d_kf1_line_record[p * line_pitch ..],
+ * d_line_pairs[p * 10 ..]. Record arrays are 16-byte aligned. Asynchronous on
+ * `stream` (a hipStream_t, NULL = the null stream), no readback. Counts above
+ * a pitch and pool indices outside [0, nkf) are clamped / skipped on the
+ * device. */
+typedef struct orblm_device_batch {
+  int32_t nkf, kp_pitch, line_pitch;
+  const int32_t* d_kf_id;
+  const int32_t* d_kf_n;
+  const float* d_kf_Tcw;
+  const orbpl_keypoint* d_kps;
+  const orbpl_keypoint* d_kps_un;
+  const float* d_uright;
+  const float* d_depth;
+  const uint8_t* d_desc;
+  const int32_t* d_feat_node;
+  const uint8_t* d_has_mp;
+  const float* d_mp_xyz;
+  const int32_t* d_kf_nl;
+  const orbpl_keyline* d_klines;
+  const uint8_t* d_ldesc;
+  const double* d_lcoef;
+  const int32_t* d_cur;
+  const int32_t* d_neigh;
+  orblm_point_record* d_points;
+  int32_t* d_n_points;
+  int32_t* d_kf1_point_record;
+  int32_t* d_pairs;
+  orblm_line_record* d_lines;
+  int32_t* d_n_lines;
+  int32_t* d_kf1_line_record;
+  int32_t* d_line_pairs;
+} orblm_device_batch;
+int orblm_create_new_map_features_batch_device(const orbpl_camera* cam, const float* scale_factors,
+                                               const float* level_sigma2, int nlevels,
+                                               const orblm_device_batch* b, int n, void* stream);
+/* ORBmatcher(nnratio, check_ori).SearchForTriangulation(pKF1, pKF2, F12,
+ * vMatchedPairs, only_stereo) alone: the one problem, one neighbour case of
+ * the same kernel without the triangulation. f12_in: F12 row-major (9
+ * floats), NULL = ComputeF12(pKF1, pKF2). pairs[2 * kf1->n]: (idx1, idx2) in
+ * KF1 index order; f12_out (9 floats, the matrix used) may be NULL. The
+ * keyframes' line fields and mp_xyz are not read. */
+int orbm_search_for_triangulation(const orbpl_camera* cam, const float* scale_factors,
+                                  const float* level_sigma2, int nlevels,
+                                  const orblm_keyframe* kf1, const orblm_keyframe* kf2,
+                                  const float* f12_in, int only_stereo, int check_ori,
+                                  int32_t* pairs, int* npairs, float* f12_out);
+/* LineMatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, .) alone
+ * (the flag is not read by the reference): pairs[2 * nl1] in KF1 line order.
+ * Only the line descriptors are read. nl1, nl2 <= 256. */
+int orbl_search_for_triangulation(int nl1, const uint8_t* ldesc1, int nl2, const uint8_t* ldesc2,
+                                  int32_t* pairs, int* npairs);
+
+/* ------------------------------------------------------------------------
  * Optimizer::PoseOptimization / PoseOptimizationWithLines
  * (Optimizer.cc:375-619, 2132-2486): 4 rounds x 10 Levenberg-Marquardt
  * iterations on one SE3 vertex, Huber kernel in rounds 0-2, chi2 outlier

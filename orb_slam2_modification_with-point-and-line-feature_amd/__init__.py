@@ -1964,3 +1964,249 @@ def _reloc_relocalize_batch_device(self, batch, n, scoring=0, stream=None):
 
 
 Relocalizer.relocalize_batch_device = _reloc_relocalize_batch_device
+
+
+# ---------------------------------------------------------------------------
+# LocalMapping::CreateNewMapPoints + CreateNewMapLines as one batched call
+# 
+# ---------------------------------------------------------------------------
+LM_MAX_KEYPOINTS, LM_MAX_LINES, LM_MAX_NEIGHBOURS = 2048, 256, 10
+LM_RECORD_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"),
+                            ("desc_from", "<i4"), ("xyz", "<f4", 3), ("normal", "<f4", 3),
+                            ("min_dist", "<f4"), ("max_dist", "<f4")])
+LM_LINE_RECORD_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"),
+                                 ("desc_from", "<i4"), ("xyz6", "<f4", 6), ("reserved", "<i4", 2)])
+
+
+class LmKeyFrame(C.Structure):
+    """orblm_keyframe"""
+    _fields_ = ([("id", C.c_int32), ("Tcw", C.c_void_p), ("n", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("kps", "kps_un", "uright", "depth", "desc",
+                                           "feat_node", "has_mp", "mp_xyz")] +
+                [("nl", C.c_int32)] + [(k, C.c_void_p) for k in ("klines", "ldesc", "lcoef")])
+
+
+class LmProblem(C.Structure):
+    """orblm_problem"""
+    _fields_ = [("cur", LmKeyFrame), ("n_neigh", C.c_int32), ("neigh", C.c_void_p),
+                ("points", C.c_void_p), ("n_points", C.c_int32),
+                ("kf1_point_record", C.c_void_p), ("pairs", C.c_int32 * LM_MAX_NEIGHBOURS),
+                ("lines", C.c_void_p), ("n_lines", C.c_int32), ("kf1_line_record", C.c_void_p),
+                ("line_pairs", C.c_int32 * LM_MAX_NEIGHBOURS)]
+
+
+class LmDeviceBatch(C.Structure):
+    """orblm_device_batch: a pitched pool of keyframes (see include/orbpl.h)"""
+    _fields_ = ([("nkf", C.c_int32), ("kp_pitch", C.c_int32), ("line_pitch", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("d_kf_id", "d_kf_n", "d_kf_Tcw", "d_kps", "d_kps_un",
+                                           "d_uright", "d_depth", "d_desc", "d_feat_node",
+                                           "d_has_mp", "d_mp_xyz", "d_kf_nl", "d_klines", "d_ldesc",
+                                           "d_lcoef", "d_cur", "d_neigh", "d_points",
+                                           "d_n_points", "d_kf1_point_record", "d_pairs", "d_lines",
+                                           "d_n_lines", "d_kf1_line_record", "d_line_pairs")])
+
+
+def _declare_localmap(L):
+    vp, i = C.c_void_p, C.c_int
+    L.orblm_create_new_map_features.argtypes = [vp, vp, vp, i, vp, i]
+    L.orblm_create_new_map_features_batch_device.argtypes = [vp, vp, vp, i, vp, i, vp]
+    L.orbm_search_for_triangulation.argtypes = [vp, vp, vp, i, vp, vp, vp, i, i, vp,
+                                                C.POINTER(C.c_int), vp]
+    L.orbl_search_for_triangulation.argtypes = [i, vp, i, vp, vp, C.POINTER(C.c_int)]
+
+
+_declare_before_localmap = _declare
+
+
+def _declare(L):  # noqa: F811
+    _declare_before_localmap(L)
+    _declare_localmap(L)
+
+
+def _lm_arrays(kf):
+    """the arrays of a keyframe dict (id, Tcw, kps, kps_un, uright, depth, desc,
+    feat_node, has_mp, mp_xyz; klines, ldesc, lcoef), absent line fields = no
+    lines, absent mp_xyz = zeros"""
+    n = len(_c(kf["uright"], np.float32))
+    a = dict(kps=_c(kf["kps"], KP_DTYPE), kps_un=_c(kf["kps_un"], KP_DTYPE),
+             uright=_c(kf["uright"], np.float32), depth=_c(kf["depth"], np.float32),
+             desc=_c(kf["desc"], np.uint8).reshape(n, 32), feat_node=_c(kf["feat_node"], np.int32),
+             has_mp=_c(kf["has_mp"], np.uint8),
+             mp_xyz=_c(kf.get("mp_xyz", np.zeros((n, 3))), np.float32).reshape(n, 3))
+    ld = _c(kf.get("ldesc", np.zeros((0, 32))), np.uint8).reshape(-1, 32)
+    a.update(klines=_c(kf.get("klines", np.zeros(0, KEYLINE_DTYPE)), KEYLINE_DTYPE), ldesc=ld,
+             lcoef=_c(kf.get("lcoef", np.zeros((0, 3))), np.float64).reshape(-1, 3))
+    return n, len(ld), a
+
+
+_LM_POINT_FIELDS = ("kps", "kps_un", "uright", "depth", "desc", "feat_node", "has_mp", "mp_xyz")
+_LM_LINE_FIELDS = ("klines", "ldesc", "lcoef")
+
+
+def _lm_keyframe(kf, keep):
+    """LmKeyFrame of a keyframe dict; the arrays it points into go to `keep`."""
+    T = _c(kf["Tcw"], np.float32).reshape(16)
+    n, nl, a = _lm_arrays(kf)
+    keep += [T, a]
+    return LmKeyFrame(int(kf["id"]), _ptr(T), n, *[_ptr(a[k]) for k in _LM_POINT_FIELDS], nl,
+                      *[_ptr(a[k]) for k in _LM_LINE_FIELDS])
+
+
+def _lm_outputs(n1, nl1, n_points, points, rec, pairs, n_lines, lines, lrec, lpairs):
+    return dict(points=points[:n_points].copy(), kf1_point_record=rec[:n1].copy(),
+                pairs=np.array(pairs, np.int32), lines=lines[:n_lines].copy(),
+                kf1_line_record=lrec[:nl1].copy(), line_pairs=np.array(lpairs, np.int32))
+
+
+class LocalMapper:
+    """LocalMapping::CreateNewMapPoints() then CreateNewMapLines()
+    (non-monocular) for many (current keyframe, <= 10 neighbours) problems in one
+    launch. A problem is dict(cur=keyframe, neigh=[keyframes]), a keyframe
+    dict(id, Tcw, kps, kps_un, uright, depth, desc, feat_node, has_mp, mp_xyz,
+    klines, ldesc, lcoef). Results per problem: points / lines (records of
+    LM_RECORD_DTYPE / LM_LINE_RECORD_DTYPE in creation order), kf1_point_record,
+    kf1_line_record, pairs[10], line_pairs[10]."""
+
+    def __init__(self, camera, scale_factors, level_sigma2):
+        self.camera = camera
+        self.scale = _c(scale_factors, np.float32)
+        self.sigma2 = _c(level_sigma2, np.float32)
+        assert len(self.scale) == len(self.sigma2)
+
+    def _consts(self):
+        return C.byref(self.camera), _ptr(self.scale), _ptr(self.sigma2), len(self.scale)
+
+    def create_new_map_features(self, problems):
+        keep, P = [], (LmProblem * max(1, len(problems)))()
+        outs = []
+        for p, prob in enumerate(problems):
+            cur = _lm_keyframe(prob["cur"], keep)
+            nb = (LmKeyFrame * max(1, len(prob["neigh"])))(
+                *[_lm_keyframe(k, keep) for k in prob["neigh"]])
+            pts = np.zeros(max(1, cur.n), LM_RECORD_DTYPE)
+            rec = np.full(max(1, cur.n), -1, np.int32)
+            lns = np.zeros(max(1, LM_MAX_NEIGHBOURS * cur.nl), LM_LINE_RECORD_DTYPE)
+            lrec = np.full(max(1, cur.nl), -1, np.int32)
+            keep += [nb, pts, rec, lns, lrec]
+            outs.append((pts, rec, lns, lrec))
+            P[p].cur, P[p].n_neigh = cur, len(prob["neigh"])
+            P[p].neigh = C.cast(nb, C.c_void_p)
+            P[p].points, P[p].kf1_point_record = _ptr(pts), _ptr(rec)
+            P[p].lines, P[p].kf1_line_record = _ptr(lns), _ptr(lrec)
+        check(lib().orblm_create_new_map_features(*self._consts(), P, len(problems)),
+              "orblm_create_new_map_features")
+        return [_lm_outputs(P[p].cur.n, P[p].cur.nl, P[p].n_points, outs[p][0], outs[p][1],
+                            list(P[p].pairs), P[p].n_lines, outs[p][2], outs[p][3],
+                            list(P[p].line_pairs)) for p in range(len(problems))]
+
+    def search_for_triangulation(self, kf1, kf2, only_stereo=False, check_ori=False, F12=None):
+        """ORBmatcher(., check_ori).SearchForTriangulation(kf1, kf2, F12, .,
+        only_stereo), F12 = ComputeF12(kf1, kf2) unless given: (pairs (n, 2) in KF1
+        index order, the F12 used)."""
+        keep = []
+        fin = None if F12 is None else _c(F12, np.float32).reshape(9)
+        a, b = _lm_keyframe(kf1, keep), _lm_keyframe(kf2, keep)
+        pairs = np.zeros((max(1, a.n), 2), np.int32)
+        n, F12 = C.c_int(0), np.zeros((3, 3), np.float32)
+        check(lib().orbm_search_for_triangulation(*self._consts(), C.byref(a), C.byref(b),
+                                                  None if fin is None else _ptr(fin),
+                                                  int(only_stereo), int(check_ori), _ptr(pairs),
+                                                  C.byref(n), _ptr(F12)),
+              "orbm_search_for_triangulation")
+        return pairs[:n.value].copy(), F12
+
+
+def line_search_for_triangulation(ldesc1, ldesc2):
+    """LineMatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, .) over the
+    two keyframes' LBD rows: pairs (n, 2) in KF1 line order."""
+    a = _c(ldesc1, np.uint8).reshape(-1, 32)
+    b = _c(ldesc2, np.uint8).reshape(-1, 32)
+    pairs, n = np.zeros((max(1, len(a)), 2), np.int32), C.c_int(0)
+    check(lib().orbl_search_for_triangulation(len(a), _ptr(a), len(b), _ptr(b), _ptr(pairs),
+                                              C.byref(n)), "orbl_search_for_triangulation")
+    return pairs[:n.value].copy()
+
+
+def search_for_triangulation(camera, scale_factors, level_sigma2, kf1, kf2, only_stereo=False,
+                             check_ori=False):
+    """LocalMapper(camera, scale_factors, level_sigma2).search_for_triangulation"""
+    return LocalMapper(camera, scale_factors, level_sigma2).search_for_triangulation(
+        kf1, kf2, only_stereo, check_ori)
+
+
+class LmDeviceProblems:
+    """The pitched device pool of orblm_create_new_map_features_batch_device for
+    a list of problems (as LocalMapper.create_new_map_features takes them): run()
+    launches without a host round trip, download() synchronises and returns the
+    same per-problem results. repeat > 1 runs the list that many times over the
+    one pool (problems are indices into it)."""
+
+    def __init__(self, mapper, problems, device=0, repeat=1):
+        self.mapper, self.device, self.ns = mapper, device, len(problems) * repeat
+        kfs, cur, neigh = [], [], []
+        for prob in problems:
+            cur.append(len(kfs))
+            kfs.append(prob["cur"])
+            row = [-1] * LM_MAX_NEIGHBOURS
+            for k, kf in enumerate(prob["neigh"]):
+                row[k] = len(kfs)
+                kfs.append(kf)
+            neigh.append(row)
+        cur, neigh = cur * repeat, neigh * repeat
+        arrs = [_lm_arrays(k) for k in kfs]
+        ns, nls = [a[0] for a in arrs], [a[1] for a in arrs]
+        self.n1 = [ns[c] for c in cur]
+        self.nl1 = [nls[c] for c in cur]
+        self.pitch = P = max([1] + ns)
+        self.line_pitch = LP = max([1] + nls)
+        K, S = max(1, len(kfs)), max(1, self.ns)
+        host = dict(kps=np.zeros((K, P), KP_DTYPE), kps_un=np.zeros((K, P), KP_DTYPE),
+                    uright=np.full((K, P), -1, np.float32), depth=np.full((K, P), -1, np.float32),
+                    desc=np.zeros((K, P, 32), np.uint8), feat_node=np.full((K, P), -1, np.int32),
+                    has_mp=np.ones((K, P), np.uint8), mp_xyz=np.zeros((K, P, 3), np.float32),
+                    klines=np.zeros((K, LP), KEYLINE_DTYPE), ldesc=np.zeros((K, LP, 32), np.uint8),
+                    lcoef=np.zeros((K, LP, 3), np.float64))
+        T, ids = np.zeros((K, 16), np.float32), np.zeros(K, np.int32)
+        for k, kf in enumerate(kfs):
+            T[k], ids[k] = _c(kf["Tcw"], np.float32).reshape(16), int(kf["id"])
+            for name in _LM_POINT_FIELDS:
+                host[name][k, :ns[k]] = arrs[k][2][name]
+            for name in _LM_LINE_FIELDS:
+                host[name][k, :nls[k]] = arrs[k][2][name]
+        mk = lambda a: DeviceBuffer.from_array(a, device)
+        pad = lambda v, n: np.array(list(v) + [0] * (n - len(v)), np.int32)
+        NB = LM_MAX_NEIGHBOURS
+        b = self.bufs = dict(id=mk(ids), n=mk(pad(ns, K)), nl=mk(pad(nls, K)), T=mk(T),
+                             cur=mk(pad(cur, S)), neigh=mk(np.array(neigh or [[-1] * NB], np.int32)),
+                             points=DeviceBuffer(S * P * LM_RECORD_DTYPE.itemsize, device),
+                             n_points=DeviceBuffer(S * 4, device), rec=DeviceBuffer(S * P * 4, device),
+                             pairs=DeviceBuffer(S * NB * 4, device),
+                             lines=DeviceBuffer(S * NB * LP * LM_LINE_RECORD_DTYPE.itemsize, device),
+                             n_lines=DeviceBuffer(S * 4, device), lrec=DeviceBuffer(S * LP * 4, device),
+                             lpairs=DeviceBuffer(S * NB * 4, device),
+                             **{k: mk(v) for k, v in host.items()})
+        self.batch = LmDeviceBatch(K, P, LP, b["id"].ptr, b["n"].ptr, b["T"].ptr, b["kps"].ptr,
+                                   b["kps_un"].ptr, b["uright"].ptr, b["depth"].ptr, b["desc"].ptr,
+                                   b["feat_node"].ptr, b["has_mp"].ptr, b["mp_xyz"].ptr, b["nl"].ptr,
+                                   b["klines"].ptr, b["ldesc"].ptr, b["lcoef"].ptr, b["cur"].ptr,
+                                   b["neigh"].ptr, b["points"].ptr, b["n_points"].ptr, b["rec"].ptr,
+                                   b["pairs"].ptr, b["lines"].ptr, b["n_lines"].ptr, b["lrec"].ptr,
+                                   b["lpairs"].ptr)
+
+    def run(self, stream=None):
+        check(lib().orblm_create_new_map_features_batch_device(
+            *self.mapper._consts(), C.byref(self.batch), self.ns, stream),
+            "orblm_create_new_map_features_batch_device")
+
+    def download(self):
+        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
+        S, P, LP, b, NB = max(1, self.ns), self.pitch, self.line_pitch, self.bufs, LM_MAX_NEIGHBOURS
+        npts, nlns = b["n_points"].download(np.int32, S), b["n_lines"].download(np.int32, S)
+        pts = b["points"].download(LM_RECORD_DTYPE, (S, P))
+        rec = b["rec"].download(np.int32, (S, P))
+        pairs = b["pairs"].download(np.int32, (S, NB))
+        lns = b["lines"].download(LM_LINE_RECORD_DTYPE, (S, NB * LP))
+        lrec = b["lrec"].download(np.int32, (S, LP))
+        lpairs = b["lpairs"].download(np.int32, (S, NB))
+        return [_lm_outputs(self.n1[s], self.nl1[s], int(npts[s]), pts[s], rec[s], pairs[s],
+                            int(nlns[s]), lns[s], lrec[s], lpairs[s]) for s in range(self.ns)]

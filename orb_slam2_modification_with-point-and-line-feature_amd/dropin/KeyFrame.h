@@ -28,6 +28,12 @@ class KeyFrame {
         mpORBvocabulary(F.mpORBvocabulary), mvpMapPoints(F.mvpMapPoints),
         Tcw(F.mTcw.clone()) {
     mnId = nNextId++;
+    fx = Frame::fx; fy = Frame::fy; cx = Frame::cx; cy = Frame::cy;
+    invfx = 1.0f / fx;
+    invfy = 1.0f / fy;
+    mbf = F.mbf;
+    mb = mbf / fx;
+    mvLevelSigma2 = F.mvLevelSigma2;
   }
 
   // KeyFrame::ComputeBoW (KeyFrame.cc:67-80)
@@ -40,6 +46,31 @@ class KeyFrame {
   std::vector<MapLine*> GetMapLineMatches() const { return mvpMapLines; }
   MapPoint* GetMapPoint(const size_t& idx) const { return mvpMapPoints[idx]; }
   cv::Mat GetPose() const { return Tcw.clone(); }
+  const float* TcwData() const { return Tcw.ptr<float>(); }
+  // what both SearchForTriangulation and LocalMapping::ComputeF12 read
+  // (KeyFrame.cc:56-131): Rcw, tcw and Ow = -Rwc * tcw (double accumulation,
+  // one rounding: DESIGN.md P6)
+  cv::Mat GetRotation() const {
+    cv::Mat R(3, 3, cv::CV_32F);
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) R.at<float>(r, c) = Tcw.at<float>(r, c);
+    return R;
+  }
+  cv::Mat GetTranslation() const {
+    cv::Mat t(3, 1, cv::CV_32F);
+    for (int r = 0; r < 3; r++) t.at<float>(r, 0) = Tcw.at<float>(r, 3);
+    return t;
+  }
+  cv::Mat GetCameraCenter() const {
+    cv::Mat Ow(3, 1, cv::CV_32F);
+    for (int r = 0; r < 3; r++) {
+      double s = (double)Tcw.at<float>(0, r) * Tcw.at<float>(0, 3);
+      s += (double)Tcw.at<float>(1, r) * Tcw.at<float>(1, 3);
+      s += (double)Tcw.at<float>(2, r) * Tcw.at<float>(2, 3);
+      Ow.at<float>(r, 0) = (float)(s * -1.0);
+    }
+    return Ow;
+  }
   bool isBad() const { return mbBad; }
   void SetBadFlag() { mbBad = true; }
   // KeyFrame::GetBestCovisibilityKeyFrames (KeyFrame.cc:250-258): the first N
@@ -71,6 +102,8 @@ class KeyFrame {
   const cv::Mat mLineDescriptors;
   std::vector<MapLine*> mvpMapLines;   // public in the fork (LineMatcher.cpp:561)
   const std::vector<float> mvScaleFactors;
+  std::vector<float> mvLevelSigma2;
+  float fx = 0, fy = 0, cx = 0, cy = 0, invfx = 0, invfy = 0, mbf = 0, mb = 0;
   ORBVocabulary* mpORBvocabulary;
 
  private:

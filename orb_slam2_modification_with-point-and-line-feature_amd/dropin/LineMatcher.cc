@@ -175,4 +175,18 @@ int LineMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* RefFrame,
   return n;
 }
 
+int LineMatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2,
+                                        std::vector<std::pair<size_t, size_t>>& vMatchedPairs,
+                                        const bool /*bOnlyStereo*/) {
+  std::vector<int32_t> pairs(2 * (size_t)(pKF1->NL > 0 ? pKF1->NL : 1));
+  int n = 0;
+  if (orbl_search_for_triangulation(pKF1->NL, pKF1->mLineDescriptors.data, pKF2->NL,
+                                    pKF2->mLineDescriptors.data, pairs.data(), &n) != ORBPL_OK)
+    throw std::runtime_error(orbpl_last_error());
+  vMatchedPairs.clear();
+  vMatchedPairs.reserve(n);
+  for (int i = 0; i < n; i++) vMatchedPairs.push_back(std::make_pair(pairs[2 * i], pairs[2 * i + 1]));
+  return n;
+}
+
 }  // namespace ORB_SLAM2

@@ -24,6 +24,12 @@ class LineMatcher {
   int SearchByProjection(Frame& CurrentFrame, KeyFrame* RefFrame);
   // Tracking::SearchLocalLines (Tracking.cc:1863): lines with mbTrackInView
   int SearchByProjection(Frame& F, const std::vector<MapLine*>& vpMapLines);
+  // LocalMapping::CreateNewMapLines (LocalMapping.cc:741; LineMatcher.cpp:
+  // 1174-1204): knnMatch of the two keyframes' LBD rows, kept where the gap to
+  // the second neighbour exceeds a tenth of its MAD (the flag is not read)
+  int SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2,
+                             std::vector<std::pair<size_t, size_t>>& vMatchedPairs,
+                             const bool bOnlyStereo);
 
   // harness overloads (LineMatcher.h:51, 56, 66): new_kls gets the projected,
   // clipped KeyLines appended; match_indices every passing (new_kls index,

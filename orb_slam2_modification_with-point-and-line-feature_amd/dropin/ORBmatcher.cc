@@ -149,4 +149,46 @@ int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, std::vector<MapPoint*>& vpM
   return n;
 }
 
+int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12,
+                                       std::vector<std::pair<size_t, size_t> >& vMatchedPairs,
+                                       const bool bOnlyStereo) {
+  KeyFrame* kfs[2] = {pKF1, pKF2};
+  std::vector<int32_t> node[2];
+  std::vector<uint8_t> has[2];
+  orblm_keyframe v[2];
+  for (int k = 0; k < 2; k++) {
+    KeyFrame* K = kfs[k];
+    node[k] = nodes_of(K->mFeatVec, K->N);
+    has[k].assign(K->N > 0 ? K->N : 1, 0);
+    for (int i = 0; i < K->N; i++) has[k][i] = K->GetMapPoint(i) != nullptr;
+    v[k] = orblm_keyframe{};
+    v[k].id = (int32_t)K->mnId;
+    v[k].Tcw = K->TcwData();
+    v[k].n = K->N;
+    v[k].kps = reinterpret_cast<const orbpl_keypoint*>(K->mvKeys.data());
+    v[k].kps_un = reinterpret_cast<const orbpl_keypoint*>(K->mvKeysUn.data());
+    v[k].uright = K->mvuRight.data();
+    v[k].depth = K->mvDepth.data();
+    v[k].desc = K->mDescriptors.data;
+    v[k].feat_node = node[k].data();
+    v[k].has_mp = has[k].data();
+  }
+  orbpl_camera cam{};
+  cam.fx = pKF2->fx; cam.fy = pKF2->fy; cam.cx = pKF2->cx; cam.cy = pKF2->cy;
+  cam.bf = pKF1->mbf;
+  float F[9];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) F[3 * r + c] = F12.at<float>(r, c);
+  std::vector<int32_t> pairs(2 * (size_t)(pKF1->N > 0 ? pKF1->N : 1));
+  int n = 0;
+  check(orbm_search_for_triangulation(&cam, pKF2->mvScaleFactors.data(), pKF2->mvLevelSigma2.data(),
+                                      (int)pKF2->mvScaleFactors.size(), &v[0], &v[1], F,
+                                      bOnlyStereo ? 1 : 0, mbCheckOrientation ? 1 : 0, pairs.data(),
+                                      &n, nullptr));
+  vMatchedPairs.clear();
+  vMatchedPairs.reserve(n);
+  for (int i = 0; i < n; i++) vMatchedPairs.push_back(std::make_pair(pairs[2 * i], pairs[2 * i + 1]));
+  return n;
+}
+
 }  // namespace ORB_SLAM2

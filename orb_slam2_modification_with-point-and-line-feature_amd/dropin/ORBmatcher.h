@@ -3,6 +3,7 @@
 // over orbm_*.
 #pragma once
 #include <set>
+#include <utility>
 #include <vector>
 
 #include "Frame.h"
@@ -37,6 +38,13 @@ class ORBmatcher {
   int SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF,
                          const std::set<MapPoint*>& sAlreadyFound, const float th,
                          const int ORBdist);
+
+  // LocalMapping::CreateNewMapPoints (LocalMapping.cc:430; ORBmatcher.h:82,
+  // ORBmatcher.cc:884-1095): pairs of features without map points that share a
+  // vocabulary node and fulfil the epipolar constraint of F12
+  int SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12,
+                             std::vector<std::pair<size_t, size_t> >& vMatchedPairs,
+                             const bool bOnlyStereo);
 
   float mfNNratio;
   bool mbCheckOrientation;

@@ -745,6 +745,90 @@ static int relocalize_mode(const char* inp, const char* outp) {
   return 0;
 }
 
+// --triangulation in.bin out.bin: ORBmatcher(0.6, checkOri).SearchForTriangulation
+// and LineMatcher::SearchForTriangulation over two keyframes.
+// in.bin : float fx fy cx cy bf; int32 nlevels; float scale[nlevels],
+//          levelSigma2[nlevels]; int32 onlyStereo, checkOri; float F12[9]; per
+//          keyframe (two): float Tcw[16]; int32 N; keysUn (N x 28 B); float
+//          uRight[N]; desc (N x 32); int32 node[N] (-1 none); u8 hasMapPoint[N];
+//          int32 NL; line desc (NL x 32)
+// out.bin: int32 n; int32 pairs[2n]; int32 nl; int32 linePairs[2nl]
+static int triangulation_mode(const char* inp, const char* outp) {
+  FILE* in = fopen(inp, "rb");
+  if (!in) throw std::runtime_error("cannot open input");
+  float camv[5], F[9];
+  int32_t nlev, flags[2];
+  rd(in, camv, 5);
+  rd(in, &nlev, 1);
+  std::vector<float> scale(nlev), sigma2(nlev);
+  rd(in, scale.data(), nlev);
+  rd(in, sigma2.data(), nlev);
+  rd(in, flags, 2);
+  rd(in, F, 9);
+  Frame::fx = camv[0]; Frame::fy = camv[1]; Frame::cx = camv[2]; Frame::cy = camv[3];
+  std::vector<std::unique_ptr<MapPoint>> mps;
+  std::vector<std::unique_ptr<KeyFrame>> kfs;
+  const float zero3[3] = {0, 0, 0};
+  const uint8_t zero32[32] = {0};
+  for (int k = 0; k < 2; k++) {
+    Frame FK;
+    FK.mbf = camv[4];
+    FK.mnScaleLevels = nlev;
+    FK.mvScaleFactors = scale;
+    FK.mvLevelSigma2 = sigma2;
+    FK.mTcw.create(4, 4, cv::CV_32F);
+    rd(in, FK.mTcw.ptr<float>(), 16);
+    int32_t N, NL;
+    rd(in, &N, 1);
+    FK.N = N;
+    FK.mvKeysUn.resize(N);
+    rd(in, FK.mvKeysUn.data(), N);
+    FK.mvKeys = FK.mvKeysUn;
+    FK.mvuRight.resize(N);
+    rd(in, FK.mvuRight.data(), N);
+    FK.mvDepth.assign(N, -1.0f);
+    FK.mDescriptors.create(N > 0 ? N : 1, 32, cv::CV_8U);
+    rd(in, FK.mDescriptors.data, (size_t)N * 32);
+    std::vector<int32_t> node(N);
+    std::vector<uint8_t> has(N);
+    rd(in, node.data(), N);
+    rd(in, has.data(), N);
+    FK.mvpMapPoints.assign(N, nullptr);
+    for (int i = 0; i < N; i++) {
+      if (node[i] >= 0) FK.mFeatVec[(DBoW2::NodeId)node[i]].push_back((unsigned)i);
+      if (!has[i]) continue;
+      mps.emplace_back(new MapPoint(zero3, zero32));
+      FK.mvpMapPoints[i] = mps.back().get();
+    }
+    rd(in, &NL, 1);
+    FK.NL = NL;
+    FK.mLineDescriptors.create(NL > 0 ? NL : 1, 32, cv::CV_8U);
+    rd(in, FK.mLineDescriptors.data, (size_t)NL * 32);
+    kfs.emplace_back(new KeyFrame(FK));
+  }
+  fclose(in);
+  cv::Mat F12(3, 3, cv::CV_32F);
+  for (int i = 0; i < 9; i++) F12.at<float>(i / 3, i % 3) = F[i];
+  ORBmatcher matcher(0.6, flags[1] != 0);
+  std::vector<std::pair<size_t, size_t>> vMatchedIndices, vLineIndices;
+  matcher.SearchForTriangulation(kfs[0].get(), kfs[1].get(), F12, vMatchedIndices, flags[0] != 0);
+  LineMatcher line_matcher;
+  line_matcher.SearchForTriangulation(kfs[0].get(), kfs[1].get(), vLineIndices, false);
+  FILE* o = fopen(outp, "wb");
+  if (!o) throw std::runtime_error("cannot open output");
+  for (const auto* v : {&vMatchedIndices, &vLineIndices}) {
+    wr1<int32_t>(o, (int32_t)v->size());
+    for (const auto& p : *v) {
+      wr1<int32_t>(o, (int32_t)p.first);
+      wr1<int32_t>(o, (int32_t)p.second);
+    }
+  }
+  fclose(o);
+  printf("dropin_driver --triangulation: %zu point pairs, %zu line pairs\n", vMatchedIndices.size(),
+         vLineIndices.size());
+  return 0;
+}
+
 static int fail_mode() {
   ORBextractor ex(1000, 1.2f, 8, 20, 7);
   cv::Mat K = cv::Mat::eye(3, 3, cv::CV_32F);
@@ -801,6 +885,14 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  if (argc == 4 && std::string(argv[1]) == "--triangulation") {
+    try {
+      return triangulation_mode(argv[2], argv[3]);
+    } catch (const std::exception& e) {
+      fprintf(stderr, "dropin_driver: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc == 4 && std::string(argv[1]) == "--stereo") {
     try {
       return stereo_mode(argv[2], argv[3]);
@@ -813,7 +905,8 @@ int main(int argc, char** argv) {
   if (argc != 3 && !timing) {
     fprintf(stderr, "usage: dropin_driver in.bin out.bin | dropin_driver --time in.bin K | "
                     "dropin_driver --reloc in.bin out.bin | dropin_driver --pnp in.bin out.bin | "
-                    "dropin_driver --relocalize in.bin out.bin\n");
+                    "dropin_driver --relocalize in.bin out.bin | dropin_driver --triangulation in.bin "
+                    "out.bin\n");
     return 2;
   }
   try {
