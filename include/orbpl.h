@@ -1223,6 +1223,10 @@ typedef struct lsdx_ctx lsdx_ctx;
 
 int lsdx_create(int width, int height, int max_batch, int device, lsdx_ctx** out);
 int lsdx_destroy(lsdx_ctx* ctx);
+/* Device-free geometry query (no HIP call): the 0.8-scaled size and the
+ * smallest region the detector fits for a width x height image, as
+ * lsdx_create would use them. Any pointer may be NULL. */
+int lsdx_describe(int width, int height, int* sw, int* sh, int* min_reg_size);
 /* LineSegmentDetector::detect (LSD_REFINE_ADV, scale 0.8) on one host image:
  * segments (x1, y1, x2, y2) in detection order. ORBPL_ERR_CAPACITY if more
  * than cap segments (n_out holds the count). */

@@ -707,6 +707,16 @@ struct LSD {
     return log_nfa;
   }
 
+  // The scaled image size, LOG_NT and the smallest region that is fitted
+  // (min_reg_size) of a W x H input.
+  size_t scaled_geometry(int W, int H) {
+    img_width = (int)std::lrint(W * SCALE);
+    img_height = (int)std::lrint(H * SCALE);
+    LOG_NT = 5 * (pmath::log10_(double(img_width)) + pmath::log10_(double(img_height))) / 2 +
+             pmath::log10_(11.0);
+    return size_t(-LOG_NT / pmath::log10_(ANG_TH / 180));
+  }
+
   // LineSegmentDetectorImpl::detect + flsd on an 8-bit image.
   void detect(const uint8_t* img, int W, int H, std::vector<float>& lines) {
     lines.clear();
@@ -722,14 +732,10 @@ struct LSD {
     fixed_gauss_kernel(ksize, sigma, k.data());
     std::vector<uint8_t> g((size_t)W * H);
     gauss_fixed(img, W, H, k.data(), ksize, g.data());
-    img_width = (int)std::lrint(W * SCALE);
-    img_height = (int)std::lrint(H * SCALE);
+    const size_t min_reg_size = scaled_geometry(W, H);
     scaled.assign((size_t)img_width * img_height, 0);
     resize_exact(g.data(), W, H, SCALE, scaled.data(), img_width, img_height);
     ll_angle(rho);
-    LOG_NT = 5 * (pmath::log10_(double(img_width)) + pmath::log10_(double(img_height))) / 2 +
-             pmath::log10_(11.0);
-    const size_t min_reg_size = size_t(-LOG_NT / pmath::log10_(p));
     used.assign((size_t)img_width * img_height, NOTUSED);
     if (tr) tr->px.assign((size_t)img_width * img_height, 0);
     std::vector<RegionPoint> reg;
@@ -987,6 +993,14 @@ void lbd_descriptor(const orbpl_keyline& kl, const int16_t* pdx, const int16_t* 
 using namespace lsdo;
 
 extern "C" {
+
+int oracle_lsd_geometry(int W, int H, int* sw, int* sh, int* min_reg_size) {
+  LSD lsd;
+  *min_reg_size = (int)lsd.scaled_geometry(W, H);
+  *sw = lsd.img_width;
+  *sh = lsd.img_height;
+  return 0;
+}
 
 int oracle_lsd_detect(const uint8_t* img, int W, int H, float* lines, int cap, int* n_out) {
   LSD lsd;

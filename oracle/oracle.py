@@ -411,6 +411,7 @@ def _setup(L):  # noqa: F811
     _setup_track_orb(L)
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     L.oracle_lsd_detect.argtypes = [vp, i, i, vp, i, vp]
+    L.oracle_lsd_geometry.argtypes = [i, i, vp, vp, vp]
     L.oracle_lsd_traffic.argtypes = [vp, i, i, vp]
     L.oracle_lsd_stages.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp]
     L.oracle_line_extract.argtypes = [vp, i, i, vp, vp, vp, i, vp, vp]
@@ -429,6 +430,14 @@ def lsd_detect(img, cap=4096):
     rc = lib().oracle_lsd_detect(_p(img), w, h, _p(out), cap, C.byref(n))
     assert rc == 0, rc
     return out[:n.value].copy()
+
+
+def lsd_geometry(w, h):
+    """(sw, sh, min_reg_size) of the detector on a w x h image: the 0.8-scaled
+    size and the smallest region that is fitted."""
+    o = np.zeros(3, np.int32)
+    lib().oracle_lsd_geometry(w, h, _p(o[0:]), _p(o[1:]), _p(o[2:]))
+    return int(o[0]), int(o[1]), int(o[2])
 
 
 LSD_TRAFFIC_KEYS = ("sort_cmp", "sort_moves", "seeds", "grow_nb", "grow_add", "grow_expand",

@@ -63,6 +63,7 @@ int oracle_vo_step(void* h, int stream, const uint8_t* gray, const float* depth,
 /* line features (lsd_oracle.cpp) */
 int oracle_lsd_traffic(const uint8_t* img, int W, int H, long long* out18);
 int oracle_lsd_detect(const uint8_t* img, int W, int H, float* lines, int cap, int* n_out);
+int oracle_lsd_geometry(int W, int H, int* sw, int* sh, int* min_reg_size);
 int oracle_lsd_stages(const uint8_t* img, int W, int H, uint8_t* scaled, double* angles,
                       uint32_t* order, int* sw, int* sh, int* n_order);
 int oracle_line_extract(const uint8_t* img, int W, int H, orbpl_keyline* kl_out, uint8_t* desc,

@@ -1113,6 +1113,7 @@ def _declare(L):  # noqa: F811
     vp, i, ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
     L.lsdx_create.argtypes = [i, i, i, i, C.POINTER(vp)]
     L.lsdx_destroy.argtypes = [vp]
+    L.lsdx_describe.argtypes = [i, i, ip, ip, ip]
     L.lsdx_detect.argtypes = [vp, vp, i, i, i, vp, i, ip]
     L.lsdx_detect_batch_device.argtypes = [vp, vp, i, i, C.c_int64]
     L.lsdx_synchronize.argtypes = [vp]
@@ -1125,6 +1126,15 @@ def _declare(L):  # noqa: F811
     L.lsdx_extract_batch_device.argtypes = [vp, vp, i, i, C.c_int64]
     L.lsdx_get_keylines.argtypes = [vp, i, vp, vp, vp, i, ip]
     L.lsdx_device_outputs.argtypes = [vp, vp, vp, vp, vp]
+
+
+def lsd_describe(width, height):
+    """Device-free geometry of a line detector: the 0.8-scaled size and the
+    smallest region that is fitted."""
+    sw, sh, mr = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib().lsdx_describe(width, height, C.byref(sw), C.byref(sh), C.byref(mr)),
+          "lsdx_describe")
+    return dict(sw=sw.value, sh=sh.value, min_reg_size=mr.value)
 
 
 class LineSegmentDetector:

@@ -183,8 +183,9 @@ __device__ __forceinline__ uint32_t umul16(uint32_t a, uint32_t b) {
 // pixels read) is loaded once with the blur halo, blurred in LDS (horizontal
 // sums as u16: 255 x 256 fits), resized in LDS, and the gradient of the core
 // kPrTW x kPrTH pixels written with the scaled image. The blurred image never
-// goes to HBM. The host checks the spans fit (lsdx_create) and the kernel
-// size is 7, else the three-kernel path runs.
+// goes to HBM. The host checks the spans fit (lsdx_create), the kernel size
+// is 7 and the source row pitch fits 16 bits (lsdx_run: umul16 below), else
+// the three-kernel path runs.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_lsd_prep(LsdGeom g, const int* __restrict__ tabs,
                                                   const uint8_t* __restrict__ img, int stride,

@@ -143,7 +143,10 @@ int lsdx_run(lsdx_ctx* c, const uint8_t* d_imgs, int batch, int stride, int64_t 
   const LsdGeom& g = c->g;
   HIP_CHECK(hipMemsetAsync(c->sc.maxq, 0, (size_t)batch * 4, s));
   HIP_CHECK(hipMemsetAsync(c->sc.err, 0, (size_t)batch * 4, s));
-  if (c->fused_prep) {
+  // k_lsd_prep multiplies source row by row pitch as 16-bit operands: a pitch
+  // above 65535 (a narrow ROI of a very wide device image) takes the
+  // three-kernel path, whose source offsets are 64-bit
+  if (c->fused_prep && stride <= 0xFFFF) {
     launch_lsd_prep(g, c->d_tabs, d_imgs, stride, frame_pitch, c->sc.scaled, c->sc.deg, c->sc.q,
                     c->sc.sd, c->sc.maxq, batch, s);
   } else {
@@ -191,6 +194,16 @@ int lsdx_check(lsdx_ctx* c, int batch) {
 }  // namespace orbpl
 
 extern "C" {
+
+int lsdx_describe(int width, int height, int* sw, int* sh, int* min_reg_size) {
+  LsdGeom g{};
+  int rc = lsd_geometry(width, height, &g);
+  if (rc) return rc;
+  if (sw) *sw = g.sw;
+  if (sh) *sh = g.sh;
+  if (min_reg_size) *min_reg_size = g.min_reg_size;
+  return ORBPL_OK;
+}
 
 int lsdx_destroy(lsdx_ctx* c) {
   if (!c) return ORBPL_OK;
