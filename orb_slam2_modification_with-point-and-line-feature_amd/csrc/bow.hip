@@ -30,6 +30,7 @@
 
 #include "../../include/orbpl.h"
 #include "block_ops.h"
+#include "host_stage.h"
 #include "orbpl_runtime.h"
 
 namespace orbpl {
@@ -237,12 +238,6 @@ int norm_of(int scoring) {
 }  // namespace orbpl
 
 using namespace orbpl;
-
-#define HIP_CHECK(expr)                                              \
-  do {                                                               \
-    hipError_t e_ = (expr);                                          \
-    if (e_ != hipSuccess) return orbpl::hip_fail(e_, #expr, __LINE__); \
-  } while (0)
 
 // One device's copy of the tree (orbv_upload): trackers on different GPUs may
 // share one vocabulary, so every device keeps its own buffers until

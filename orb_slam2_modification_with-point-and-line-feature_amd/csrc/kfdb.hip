@@ -25,6 +25,7 @@
 
 #include "../../include/orbpl.h"
 #include "block_ops.h"
+#include "host_stage.h"
 #include "orbpl_runtime.h"
 #include "reloc_kernels.h"
 
@@ -217,24 +218,6 @@ void launch_kfdb_reloc(const KfdbArgs& a, int nq, hipStream_t s) {
 
 using namespace orbpl;
 
-#define HIP_CHECK(expr)                                                \
-  do {                                                                 \
-    hipError_t _e = (expr);                                            \
-    if (_e != hipSuccess) return orbpl::hip_fail(_e, #expr, __LINE__); \
-  } while (0)
-
-namespace {
-struct DBuf {
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
-};
-}  // namespace
-
 extern "C" {
 
 int orbkf_detect_reloc_batch_device(const orbkf_device_batch* b, int nq, int scoring,
@@ -299,35 +282,30 @@ int orbkf_detect_reloc(const orbkf_problem* P, int nq, int scoring) {
     std::copy(r.covis, r.covis + r.nkf * kKfdbCovis, h_cov.begin() + p * K * kKfdbCovis);
     std::copy(r.reloc_score, r.reloc_score + r.nkf, h_rs.begin() + p * K);
   }
-  DBuf d_nkf, d_off, d_kw, d_kv, d_cov, d_rs, d_qn, d_qw, d_qv, d_cand, d_nc, d_cw;
-#define UP(d, h)                                                                  \
-  HIP_CHECK(d.alloc(h.size() * sizeof(h[0])));                                    \
-  HIP_CHECK(hipMemcpy(d.p, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice))
-  UP(d_nkf, h_nkf);
-  UP(d_off, h_off);
-  UP(d_kw, h_kw);
-  UP(d_kv, h_kv);
-  UP(d_cov, h_cov);
-  UP(d_rs, h_rs);
-  UP(d_qn, h_qn);
-  UP(d_qw, h_qw);
-  UP(d_qv, h_qv);
-#undef UP
-  HIP_CHECK(d_cand.alloc(Q * K * 4));
-  HIP_CHECK(d_nc.alloc(Q * 4));
-  HIP_CHECK(d_cw.alloc(Q * K * 4));
-  HIP_CHECK(hipMemset(d_cw.p, 0, Q * K * 4));
-  KfdbArgs a{d_nkf.as<int>(), d_off.as<int>(), d_kw.as<uint32_t>(), d_kv.as<double>(),
-             (long long)entp, d_cov.as<int>(), d_rs.as<float>(), d_qn.as<int>(),
-             d_qw.as<uint32_t>(), d_qv.as<double>(), (long long)qp, d_cand.as<int>(),
-             d_nc.as<int>(), d_cw.as<int>()};
+  HostStage st;
+  KfdbArgs a{st.in(h_nkf),
+             st.in(h_off),
+             st.in(h_kw),
+             st.in(h_kv),
+             (long long)entp,
+             st.in(h_cov),
+             st.in(h_rs),
+             st.in(h_qn),
+             st.in(h_qw),
+             st.in(h_qv),
+             (long long)qp,
+             st.out<int>(Q * K),
+             st.out<int>(Q),
+             st.zeros<int>(Q * K)};
+  if (st.rc()) return st.rc();
   launch_kfdb_reloc(a, nq, nullptr);   // host-pointer APIs use the null stream
-  HIP_CHECK(hipGetLastError());
+  st.launched();
   std::vector<int> h_cand(Q * K), h_nc(Q), h_cw(Q * K);
-  HIP_CHECK(hipMemcpy(h_cand.data(), d_cand.p, Q * K * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_nc.data(), d_nc.p, Q * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_cw.data(), d_cw.p, Q * K * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_rs.data(), d_rs.p, Q * K * 4, hipMemcpyDeviceToHost));
+  st.back(h_cand, a.cand);
+  st.back(h_nc, a.ncand);
+  st.back(h_cw, a.common_words);
+  st.back(h_rs, a.reloc_score);
+  if (st.rc()) return st.rc();
   for (size_t p = 0; p < Q; p++) {
     const orbkf_problem& r = P[p];
     *r.ncand = h_nc[p];

@@ -40,6 +40,7 @@
 #include "block_ops.h"
 #include "localmap_core.h"
 #include "match_common.h"
+#include "host_stage.h"
 #include "orbpl_runtime.h"
 
 namespace orbpl {
@@ -521,23 +522,7 @@ int check_batch(const orblm_device_batch* b) {
 
 using namespace orbpl;
 
-#define HIP_CHECK(expr)                                                \
-  do {                                                                 \
-    hipError_t _e = (expr);                                            \
-    if (_e != hipSuccess) return orbpl::hip_fail(_e, #expr, __LINE__); \
-  } while (0)
-
 namespace {
-
-struct DBuf {
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 // what of a keyframe a call reads
 enum { kReadPoints = 1, kReadLines = 2, kReadMapPoints = 4 };
@@ -567,10 +552,10 @@ struct HostPool {
   std::vector<const orblm_keyframe*> kfs;
   std::vector<int32_t> cur, neigh;
   int pitch = 1, lpitch = 1, reads = kReadPoints | kReadLines | kReadMapPoints;
-  DBuf id, n, T, kps, kun, ur, dep, desc, node, hmp, mpx, nl, kl, ld, lc, dcur, dneigh, pts, npts,
-      rec, pairs, lns, nlns, lrec, lpairs;
+  HostStage st;
   orblm_device_batch b{};
 
+  // stages the pool and the outputs of nprob problems into b; returns st.rc()
   int upload(int nprob) {
     const size_t K = kfs.size(), P = (size_t)pitch, LP = (size_t)lpitch;
     std::vector<int32_t> hid(K), hn(K, 0), hnl(K, 0), hnode(K * P, -1);
@@ -601,65 +586,36 @@ struct HostPool {
         memcpy(&hlc[k * LP * 3], f.lcoef, (size_t)f.nl * 24);
       }
     }
-#define UP(d, h)                                       \
-  HIP_CHECK(d.alloc(h.size() * sizeof(h[0])));         \
-  HIP_CHECK(hipMemcpy(d.p, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice))
-    UP(id, hid);
-    UP(n, hn);
-    UP(T, hT);
-    UP(kps, hk);
-    UP(kun, hu);
-    UP(ur, hur);
-    UP(dep, hdep);
-    UP(desc, hdesc);
-    UP(node, hnode);
-    UP(hmp, hh);
-    UP(mpx, hmpx);
-    UP(nl, hnl);
-    UP(kl, hkl);
-    UP(ld, hld);
-    UP(lc, hlc);
-    UP(dcur, cur);
-    UP(dneigh, neigh);
-#undef UP
     const size_t N = (size_t)nprob;
-    HIP_CHECK(pts.alloc(N * P * sizeof(orblm_point_record)));
-    HIP_CHECK(npts.alloc(N * 4));
-    HIP_CHECK(rec.alloc(N * P * 4));
-    HIP_CHECK(pairs.alloc(N * lm::kNeighbours * 4));
-    HIP_CHECK(lns.alloc(N * lm::kNeighbours * LP * sizeof(orblm_line_record)));
-    HIP_CHECK(nlns.alloc(N * 4));
-    HIP_CHECK(lrec.alloc(N * LP * 4));
-    HIP_CHECK(lpairs.alloc(N * lm::kNeighbours * 4));
     b.nkf = (int)K;
     b.kp_pitch = pitch;
     b.line_pitch = lpitch;
-    b.d_kf_id = id.as<int32_t>();
-    b.d_kf_n = n.as<int32_t>();
-    b.d_kf_Tcw = T.as<float>();
-    b.d_kps = kps.as<orbpl_keypoint>();
-    b.d_kps_un = kun.as<orbpl_keypoint>();
-    b.d_uright = ur.as<float>();
-    b.d_depth = dep.as<float>();
-    b.d_desc = desc.as<uint8_t>();
-    b.d_feat_node = node.as<int32_t>();
-    b.d_has_mp = hmp.as<uint8_t>();
-    b.d_mp_xyz = mpx.as<float>();
-    b.d_kf_nl = nl.as<int32_t>();
-    b.d_klines = kl.as<orbpl_keyline>();
-    b.d_ldesc = ld.as<uint8_t>();
-    b.d_lcoef = lc.as<double>();
-    b.d_cur = dcur.as<int32_t>();
-    b.d_neigh = dneigh.as<int32_t>();
-    b.d_points = pts.as<orblm_point_record>();
-    b.d_n_points = npts.as<int32_t>();
-    b.d_kf1_point_record = rec.as<int32_t>();
-    b.d_pairs = pairs.as<int32_t>();
-    b.d_lines = lns.as<orblm_line_record>();
-    b.d_n_lines = nlns.as<int32_t>();
-    b.d_kf1_line_record = lrec.as<int32_t>();
-    b.d_line_pairs = lpairs.as<int32_t>();
-    return ORBPL_OK;
+    b.d_kf_id = st.in(hid);
+    b.d_kf_n = st.in(hn);
+    b.d_kf_Tcw = st.in(hT);
+    b.d_kps = st.in(hk);
+    b.d_kps_un = st.in(hu);
+    b.d_uright = st.in(hur);
+    b.d_depth = st.in(hdep);
+    b.d_desc = st.in(hdesc);
+    b.d_feat_node = st.in(hnode);
+    b.d_has_mp = st.in(hh);
+    b.d_mp_xyz = st.in(hmpx);
+    b.d_kf_nl = st.in(hnl);
+    b.d_klines = st.in(hkl);
+    b.d_ldesc = st.in(hld);
+    b.d_lcoef = st.in(hlc);
+    b.d_cur = st.in(cur);
+    b.d_neigh = st.in(neigh);
+    b.d_points = st.out<orblm_point_record>(N * P);
+    b.d_n_points = st.out<int32_t>(N);
+    b.d_kf1_point_record = st.out<int32_t>(N * P);
+    b.d_pairs = st.out<int32_t>(N * lm::kNeighbours);
+    b.d_lines = st.out<orblm_line_record>(N * lm::kNeighbours * LP);
+    b.d_n_lines = st.out<int32_t>(N);
+    b.d_kf1_line_record = st.out<int32_t>(N * LP);
+    b.d_line_pairs = st.out<int32_t>(N * lm::kNeighbours);
+    return st.rc();
   }
 
   void add_keyframe(const orblm_keyframe* k) {
@@ -729,20 +685,21 @@ int orblm_create_new_map_features(const orbpl_camera* cam, const float* scale_fa
   if ((rc = H.upload(n))) return rc;
   a.b = H.b;
   launch(a, n, nullptr);   // host-pointer APIs use the null stream
-  HIP_CHECK(hipGetLastError());
+  H.st.launched();
   const size_t P = (size_t)H.pitch, LP = (size_t)H.lpitch, NB = lm::kNeighbours;
   std::vector<int32_t> hn(n), hpairs((size_t)n * NB), hrec((size_t)n * P), hnl(n),
       hlpairs((size_t)n * NB), hlrec((size_t)n * LP);
   std::vector<orblm_point_record> hp((size_t)n * P);
   std::vector<orblm_line_record> hl((size_t)n * NB * LP);
-  HIP_CHECK(hipMemcpy(hn.data(), H.npts.p, hn.size() * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(hpairs.data(), H.pairs.p, hpairs.size() * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(hrec.data(), H.rec.p, hrec.size() * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(hp.data(), H.pts.p, hp.size() * sizeof(hp[0]), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(hnl.data(), H.nlns.p, hnl.size() * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(hlpairs.data(), H.lpairs.p, hlpairs.size() * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(hlrec.data(), H.lrec.p, hlrec.size() * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(hl.data(), H.lns.p, hl.size() * sizeof(hl[0]), hipMemcpyDeviceToHost));
+  H.st.back(hn, H.b.d_n_points);
+  H.st.back(hpairs, H.b.d_pairs);
+  H.st.back(hrec, H.b.d_kf1_point_record);
+  H.st.back(hp, H.b.d_points);
+  H.st.back(hnl, H.b.d_n_lines);
+  H.st.back(hlpairs, H.b.d_line_pairs);
+  H.st.back(hlrec, H.b.d_kf1_line_record);
+  H.st.back(hl, H.b.d_lines);
+  if (H.st.rc()) return H.st.rc();
   for (int p = 0; p < n; p++) {
     orblm_problem& r = problems[p];
     r.n_points = hn[p];
@@ -776,28 +733,27 @@ int orbm_search_for_triangulation(const orbpl_camera* cam, const float* scale_fa
     return rc;
   if (kf1->n > 0 && !pairs) return arg_fail("NULL pairs");
   H.add_problem(kf1, kf2, 1);
-  if ((rc = H.upload(1))) return rc;
-  DBuf dpairs, df;
-  HIP_CHECK(dpairs.alloc((size_t)H.pitch * 8));
-  HIP_CHECK(df.alloc(9 * 4));
+  H.upload(1);
   a.b = H.b;
   a.match_only = 1;
   a.only_stereo = only_stereo != 0;
   a.check_ori = check_ori != 0;
-  a.pairs_out = dpairs.as<int32_t>();
-  a.f12_out = df.as<float>();
+  a.pairs_out = H.st.out<int32_t>(2 * (size_t)H.pitch);
+  a.f12_out = H.st.out<float>(9);
   if (f12_in) {
     a.use_f12 = 1;
     std::copy(f12_in, f12_in + 9, a.f12_in);
   }
+  if (H.st.rc()) return H.st.rc();
   launch(a, 1, nullptr);
-  HIP_CHECK(hipGetLastError());
+  H.st.launched();
   int32_t hpairs[lm::kNeighbours];
-  HIP_CHECK(hipMemcpy(hpairs, H.pairs.p, sizeof(hpairs), hipMemcpyDeviceToHost));
+  H.st.back(hpairs, H.b.d_pairs, lm::kNeighbours);
+  if (H.st.rc()) return H.st.rc();
   *npairs = std::max(hpairs[0], 0);
-  if (*npairs) HIP_CHECK(hipMemcpy(pairs, dpairs.p, (size_t)*npairs * 8, hipMemcpyDeviceToHost));
-  if (f12_out) HIP_CHECK(hipMemcpy(f12_out, df.p, 36, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
+  H.st.back(pairs, a.pairs_out, 2 * (size_t)*npairs);
+  if (f12_out) H.st.back(f12_out, a.f12_out, 9);
+  return H.st.rc();
 }
 
 int orbl_search_for_triangulation(int nl1, const uint8_t* ldesc1, int nl2, const uint8_t* ldesc2,
@@ -822,20 +778,19 @@ int orbl_search_for_triangulation(int nl1, const uint8_t* ldesc1, int nl2, const
   HostPool H;
   H.reads = kReadLines;
   H.add_problem(&k1, &k2, 1);
-  int rc;
-  if ((rc = H.upload(1))) return rc;
-  DBuf dpairs;
-  HIP_CHECK(dpairs.alloc((size_t)H.lpitch * 8));
+  H.upload(1);
   a.b = H.b;
   a.match_only = 2;
-  a.pairs_out = dpairs.as<int32_t>();
+  a.pairs_out = H.st.out<int32_t>(2 * (size_t)H.lpitch);
+  if (H.st.rc()) return H.st.rc();
   launch(a, 1, nullptr);
-  HIP_CHECK(hipGetLastError());
+  H.st.launched();
   int32_t hpairs[lm::kNeighbours];
-  HIP_CHECK(hipMemcpy(hpairs, H.lpairs.p, sizeof(hpairs), hipMemcpyDeviceToHost));
+  H.st.back(hpairs, H.b.d_line_pairs, lm::kNeighbours);
+  if (H.st.rc()) return H.st.rc();
   *npairs = std::max(hpairs[0], 0);
-  if (*npairs) HIP_CHECK(hipMemcpy(pairs, dpairs.p, (size_t)*npairs * 8, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
+  H.st.back(pairs, a.pairs_out, 2 * (size_t)*npairs);
+  return H.st.rc();
 }
 
 }  // extern "C"

@@ -13,15 +13,10 @@
 #include "../../include/orbpl.h"
 #include "lsd_kernels.h"
 #include "lsd_math.h"
+#include "host_stage.h"
 #include "orbpl_runtime.h"
 
 using namespace orbpl;
-
-#define HIP_CHECK(expr)                                              \
-  do {                                                               \
-    hipError_t _e = (expr);                                          \
-    if (_e != hipSuccess) return orbpl::hip_fail(_e, #expr, __LINE__); \
-  } while (0)
 
 namespace {
 

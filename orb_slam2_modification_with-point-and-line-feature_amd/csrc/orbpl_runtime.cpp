@@ -18,6 +18,7 @@
 
 #include "../../include/orbpl.h"
 #include "orb_kernels.h"
+#include "host_stage.h"
 #include "orbpl_runtime.h"
 
 namespace orbpl {
@@ -179,12 +180,6 @@ struct orbx_ctx {
   int* d_err = nullptr;
   int last_batch = 0;
 };
-
-#define HIP_CHECK(expr)                                              \
-  do {                                                               \
-    hipError_t _e = (expr);                                          \
-    if (_e != hipSuccess) return orbpl::hip_fail(_e, #expr, __LINE__); \
-  } while (0)
 
 extern "C" {
 

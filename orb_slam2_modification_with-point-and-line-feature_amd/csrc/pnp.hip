@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/orbpl.h"
+#include "host_stage.h"
 #include "orbpl_runtime.h"
 #include "pnp_core.h"
 #include "reloc_kernels.h"
@@ -281,23 +282,7 @@ void launch_pnp_iterate(const PnpArgs& a, int nsolvers, hipStream_t s) {
 
 using namespace orbpl;
 
-#define HIP_CHECK(expr)                                                \
-  do {                                                                 \
-    hipError_t _e = (expr);                                            \
-    if (_e != hipSuccess) return orbpl::hip_fail(_e, #expr, __LINE__); \
-  } while (0)
-
 namespace {
-struct DBuf {
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
-};
-
 // hypotheses iterate(n_iterations) runs at most from this state
 long long pnp_hypotheses(int n, int min_inliers, int max_its, int iterations, int n_iterations) {
   if (n < min_inliers) return 0;
@@ -401,50 +386,46 @@ int orbpnp_iterate(const orbpnp_problem* P, int nsolvers, int n_iterations) {
     std::copy(r.max_error, r.max_error + r.n, h_me.begin() + p * ptp);
     std::copy(r.best_mask, r.best_mask + r.n, h_bm.begin() + p * ptp);
   }
-  DBuf d_n, d_min, d_max, d_dr, d_it, d_best, d_cam, d_p2, d_p3, d_me, d_bT, d_bm, d_T, d_res,
-      d_nm, d_ni, d_inl, d_dc;
-#define UP(d, h)                                                                  \
-  HIP_CHECK(d.alloc(h.size() * sizeof(h[0])));                                    \
-  HIP_CHECK(hipMemcpy(d.p, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice))
-  UP(d_n, h_n);
-  UP(d_min, h_min);
-  UP(d_max, h_max);
-  UP(d_dr, h_dr);
-  UP(d_it, h_it);
-  UP(d_best, h_best);
-  UP(d_cam, h_cam);
-  UP(d_p2, h_p2);
-  UP(d_p3, h_p3);
-  UP(d_me, h_me);
-  UP(d_bT, h_bT);
-  UP(d_bm, h_bm);
-#undef UP
-  HIP_CHECK(d_T.alloc(S * 16 * 4));
-  HIP_CHECK(d_res.alloc(S * 4));
-  HIP_CHECK(d_nm.alloc(S * 4));
-  HIP_CHECK(d_ni.alloc(S * 4));
-  HIP_CHECK(d_inl.alloc(S * ptp));
-  HIP_CHECK(d_dc.alloc(S * 4));
-  PnpArgs a{d_n.as<int>(), d_cam.as<float>(), d_p2.as<float>(), d_p3.as<float>(),
-            d_me.as<float>(), (int)ptp, d_min.as<int>(), d_max.as<int>(), d_dr.as<int>(),
-            (int)drp, (double)RAND_MAX + 1.0, n_iterations, d_it.as<int>(), d_best.as<int>(),
-            d_bm.as<uint8_t>(), d_bT.as<float>(), d_T.as<float>(), d_res.as<int>(),
-            d_nm.as<int>(), d_ni.as<int>(), d_inl.as<uint8_t>(), d_dc.as<int>()};
+  HostStage st;
+  PnpArgs a{st.in(h_n),
+            st.in(h_cam),
+            st.in(h_p2),
+            st.in(h_p3),
+            st.in(h_me),
+            (int)ptp,
+            st.in(h_min),
+            st.in(h_max),
+            st.in(h_dr),
+            (int)drp,
+            (double)RAND_MAX + 1.0,
+            n_iterations,
+            st.in(h_it),
+            st.in(h_best),
+            st.in(h_bm),
+            st.in(h_bT),
+            st.out<float>(S * 16),
+            st.out<int>(S),
+            st.out<int>(S),
+            st.out<int>(S),
+            st.out<uint8_t>(S * ptp),
+            st.out<int>(S)};
+  if (st.rc()) return st.rc();
   launch_pnp_iterate(a, nsolvers, nullptr);   // host-pointer APIs use the null stream
-  HIP_CHECK(hipGetLastError());
+  st.launched();
   std::vector<int> h_res(S), h_nm(S), h_ni(S), h_dc(S);
   std::vector<float> h_T(S * 16);
   std::vector<uint8_t> h_inl(S * ptp);
-  HIP_CHECK(hipMemcpy(h_res.data(), d_res.p, S * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_nm.data(), d_nm.p, S * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_ni.data(), d_ni.p, S * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_dc.data(), d_dc.p, S * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_T.data(), d_T.p, S * 64, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_inl.data(), d_inl.p, S * ptp, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_it.data(), d_it.p, S * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_best.data(), d_best.p, S * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_bT.data(), d_bT.p, S * 64, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_bm.data(), d_bm.p, S * ptp, hipMemcpyDeviceToHost));
+  st.back(h_res, a.result);
+  st.back(h_nm, a.no_more);
+  st.back(h_ni, a.n_inliers);
+  st.back(h_dc, a.draws_consumed);
+  st.back(h_T, a.Tcw);
+  st.back(h_inl, a.inliers);
+  st.back(h_it, a.iterations);
+  st.back(h_best, a.best_count);
+  st.back(h_bT, a.best_Tcw);
+  st.back(h_bm, a.best_mask);
+  if (st.rc()) return st.rc();
   for (size_t p = 0; p < S; p++) {
     const orbpnp_problem& r = P[p];
     *r.iterations = h_it[p];

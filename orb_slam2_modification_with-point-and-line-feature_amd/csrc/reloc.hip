@@ -22,6 +22,7 @@
 
 #include "../../include/orbpl.h"
 #include "block_ops.h"
+#include "host_stage.h"
 #include "orbpl_runtime.h"
 #include "reloc_kernels.h"
 #include "track_kernels.h"
@@ -402,12 +403,6 @@ void launch_reloc_select(const RelocDev& d, hipStream_t s) {
 
 using namespace orbpl;
 
-#define HIP_CHECK(expr)                                                \
-  do {                                                                 \
-    hipError_t _e = (expr);                                            \
-    if (_e != hipSuccess) return orbpl::hip_fail(_e, #expr, __LINE__); \
-  } while (0)
-
 namespace {
 
 // a device buffer that only grows
@@ -429,6 +424,14 @@ struct Grow {
   template <class T>
   T* as() const { return reinterpret_cast<T*>(p); }
 };
+
+// grow g to h's size and copy h into it; does nothing once *e is a failure
+template <class T>
+T* upload(Grow& g, const std::vector<T>& h, hipError_t* e) {
+  if (*e == hipSuccess) *e = g.need(h.size() * sizeof(T));
+  if (*e == hipSuccess) *e = hipMemcpy(g.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+  return g.as<T>();
+}
 
 constexpr int kNumIn = 28, kNumPair = 52, kNumProb = 16;
 
@@ -638,11 +641,12 @@ int orbrl_create(const orbpl_camera* cam, const float* scale_factors, const floa
     inv[l] = 1.0f / level_sigma2[l];   // ORBextractor's mvInvLevelSigma2
   }
   for (int l = nlevels; l < kMaxLevelsT; l++) h->sigma2[l] = level_sigma2[nlevels - 1];
-  int rc = reloc_consts(cam, scale_factors, inv, nlevels, &h->consts, &h->log_scale);
+  int rc = make_consts(cam, scale_factors, inv, nlevels, &h->consts);
   if (rc) {
     delete h;
     return rc;
   }
+  h->log_scale = log_scale_of(scale_factors, nlevels);   // as orbm_search_by_projection_kf takes it
   h->cam[0] = cam->fx;
   h->cam[1] = cam->fy;
   h->cam[2] = cam->cx;
@@ -846,37 +850,34 @@ int orbrl_relocalize(orbrl_handle* h, orbrl_problem* probs, int n, int scoring) 
   }
   Grow* g = h->in;
   int gi = 0;
-#define UP(var, hv)                                                                            \
-  HIP_CHECK(g[gi].need(hv.size() * sizeof(hv[0])));                                            \
-  HIP_CHECK(hipMemcpy(g[gi].p, hv.data(), hv.size() * sizeof(hv[0]), hipMemcpyHostToDevice)); \
-  auto* var = g[gi++].as<std::remove_reference<decltype(hv[0])>::type>()
-  UP(d_nkf, h_nkf);
-  UP(d_off, h_off);
-  UP(d_cov, h_cov);
-  UP(d_qn, h_qn);
-  UP(d_n, h_n);
-  UP(d_fnode, h_fnode);
-  UP(d_kfn, h_kfn);
-  UP(d_kfnode, h_kfnode);
-  UP(d_draws, h_draws);
-  UP(d_ns, h_ns);
-  UP(d_kw, h_kw);
-  UP(d_qw, h_qw);
-  UP(d_kv, h_kv);
-  UP(d_qv, h_qv);
-  UP(d_rs, h_rs);
-  UP(d_ur, h_ur);
-  UP(d_kang, h_kang);
-  UP(d_xyz, h_xyz);
-  UP(d_mn, h_mn);
-  UP(d_mx, h_mx);
-  UP(d_kps, h_kps);
-  UP(d_desc, h_desc);
-  UP(d_kdesc, h_kdesc);
-  UP(d_kval, h_kval);
-  UP(d_mdesc, h_mdesc);
-  UP(d_first, kf_first);
-#undef UP
+  hipError_t e = hipSuccess;
+  auto* d_nkf = upload(g[gi++], h_nkf, &e);
+  auto* d_off = upload(g[gi++], h_off, &e);
+  auto* d_cov = upload(g[gi++], h_cov, &e);
+  auto* d_qn = upload(g[gi++], h_qn, &e);
+  auto* d_n = upload(g[gi++], h_n, &e);
+  auto* d_fnode = upload(g[gi++], h_fnode, &e);
+  auto* d_kfn = upload(g[gi++], h_kfn, &e);
+  auto* d_kfnode = upload(g[gi++], h_kfnode, &e);
+  auto* d_draws = upload(g[gi++], h_draws, &e);
+  auto* d_ns = upload(g[gi++], h_ns, &e);
+  auto* d_kw = upload(g[gi++], h_kw, &e);
+  auto* d_qw = upload(g[gi++], h_qw, &e);
+  auto* d_kv = upload(g[gi++], h_kv, &e);
+  auto* d_qv = upload(g[gi++], h_qv, &e);
+  auto* d_rs = upload(g[gi++], h_rs, &e);
+  auto* d_ur = upload(g[gi++], h_ur, &e);
+  auto* d_kang = upload(g[gi++], h_kang, &e);
+  auto* d_xyz = upload(g[gi++], h_xyz, &e);
+  auto* d_mn = upload(g[gi++], h_mn, &e);
+  auto* d_mx = upload(g[gi++], h_mx, &e);
+  auto* d_kps = upload(g[gi++], h_kps, &e);
+  auto* d_desc = upload(g[gi++], h_desc, &e);
+  auto* d_kdesc = upload(g[gi++], h_kdesc, &e);
+  auto* d_kval = upload(g[gi++], h_kval, &e);
+  auto* d_mdesc = upload(g[gi++], h_mdesc, &e);
+  auto* d_first = upload(g[gi++], kf_first, &e);
+  HIP_CHECK(e);
   Grow& g_cand = g[gi++];
   Grow& g_nc = g[gi++];
   static_assert(kNumIn == 28, "one Grow per input array");

@@ -226,9 +226,4 @@ void launch_reloc_after_pnp(const RelocDev& d, hipStream_t s);
 void launch_reloc_stage(const RelocDev& d, int phase, hipStream_t s);   // then the pose list
 void launch_reloc_select(const RelocDev& d, hipStream_t s);
 
-// Frame constants for the relocalisation call (track_runtime.cpp's make_consts;
-// cam is an orbpl_camera)
-int reloc_consts(const void* cam, const float* scale, const float* inv_sigma2, int nlevels,
-                 TrackConsts* out, float* log_scale);
-
 }  // namespace orbpl

@@ -446,4 +446,14 @@ void launch_finish(const TrackConsts& c, StreamState* st, const int* n, int kp_p
                    uint8_t* has_mp, float* mp_xyz, int* nobs, const LineFinish& lf, int nstreams,
                    hipStream_t s, int local_map = 0);
 
+// Host side (track_host.cpp). Frame constants (Frame.cc:180-203) from the
+// camera and the extractor's scale tables (NULL: all 1).
+int make_consts(const orbpl_camera* cam, const float* scale, const float* inv_sigma2, int nlevels,
+                TrackConsts* out);
+// Frame::mfLogScaleFactor = log(mfScaleFactor) on a float (P15)
+float log_scale_of(float scale_factor);
+// the same from the extractor's table: mvScaleFactors[1] is 1.0f * mfScaleFactor.
+// One level: PredictScale always gives level 0.
+float log_scale_of(const float* scale_factors, int nlevels);
+
 }  // namespace orbpl

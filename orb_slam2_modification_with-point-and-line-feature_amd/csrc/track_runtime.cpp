@@ -1,7 +1,6 @@
-// Host runtime + C-ABI of the tracking half of the hot path:
-// orbpl_frame_prepare / orbm_search_by_projection_last / orbpl_pose_optimization
-// (single-frame host-pointer forms, drop-in for Frame / ORBmatcher / Optimizer
-// calls) and the batched device-resident orbpl_tracker.
+// Host runtime + C-ABI of the tracking half of the hot path: the batched
+// device-resident orbpl_tracker. (The single-frame host-pointer forms are in
+// track_host.cpp.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,21 +11,14 @@
 #include <vector>
 
 #include "../../include/orbpl.h"
+#include "host_stage.h"
 #include "orb_kernels.h"
 #include "orbpl_runtime.h"
 #include "track_kernels.h"
 #include "lsd_kernels.h"
-#include "lsd_math.h"
 #include "map_kernels.h"
-#include "reloc_kernels.h"
 
 using namespace orbpl;
-
-#define HIP_CHECK(expr)                                                \
-  do {                                                                 \
-    hipError_t _e = (expr);                                            \
-    if (_e != hipSuccess) return orbpl::hip_fail(_e, #expr, __LINE__); \
-  } while (0)
 
 namespace {
 
@@ -51,933 +43,11 @@ bool split_on(const char* env, int n_streams, int min_streams) {
   return e ? e[0] == '1' : n_streams >= min_streams && enough_hw_queues();
 }
 
-// RAII device buffer for the synchronous host-pointer entry points.
-struct DBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  hipError_t alloc(size_t bytes) {
-    n = bytes;
-    return hipMalloc(&p, bytes ? bytes : 1);
-  }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// Frame constants (Frame.cc:180-203) from the camera and the extractor's
-// scale tables; ComputeImageBounds uses the same undistortion code as the
-// device kernel (host-compiled, same IEEE double sequence).
-int make_consts(const orbpl_camera* cam, const float* scale, const float* inv_sigma2, int nlevels,
-                TrackConsts* out) {
-  if (!cam) return arg_fail("NULL camera");
-  if (nlevels < 1 || nlevels > kMaxLevelsT) return arg_fail("nlevels out of range");
-  TrackConsts c{};
-  c.fx = cam->fx; c.fy = cam->fy; c.cx = cam->cx; c.cy = cam->cy;
-  c.k1 = cam->k1; c.k2 = cam->k2; c.p1 = cam->p1; c.p2 = cam->p2; c.k3 = cam->k3;
-  c.bf = cam->bf;
-  c.mb = cam->bf / cam->fx;
-  c.th_depth = cam->th_depth;
-  c.invfx = 1.0f / cam->fx;
-  c.invfy = 1.0f / cam->fy;
-  c.width = cam->width;
-  c.height = cam->height;
-  if (cam->k1 != 0.0f) {
-    float ux[4], uy[4];
-    const float px[4] = {0.0f, (float)cam->width, 0.0f, (float)cam->width};
-    const float py[4] = {0.0f, 0.0f, (float)cam->height, (float)cam->height};
-    for (int i = 0; i < 4; i++) undistort_point_d(c, px[i], py[i], &ux[i], &uy[i]);
-    c.minX = std::min(ux[0], ux[2]);
-    c.maxX = std::max(ux[1], ux[3]);
-    c.minY = std::min(uy[0], uy[1]);
-    c.maxY = std::max(uy[2], uy[3]);
-  } else {
-    c.minX = 0.0f; c.maxX = (float)cam->width; c.minY = 0.0f; c.maxY = (float)cam->height;
-  }
-  c.gridInvW = static_cast<float>(kGridCols) / static_cast<float>(c.maxX - c.minX);
-  c.gridInvH = static_cast<float>(kGridRows) / static_cast<float>(c.maxY - c.minY);
-  c.nlevels = nlevels;
-  for (int l = 0; l < nlevels; l++) {
-    c.scale[l] = scale ? scale[l] : 1.0f;
-    c.inv_sigma2[l] = inv_sigma2 ? inv_sigma2[l] : 1.0f;
-  }
-  *out = c;
-  return ORBPL_OK;
-}
-
-hipStream_t scratch_stream() { return nullptr; }  // host-pointer APIs use the null stream
-
 }  // namespace
-
-int orbpl::reloc_consts(const void* cam, const float* scale, const float* inv_sigma2, int nlevels,
-                        TrackConsts* out, float* log_scale) {
-  const int rc = make_consts(static_cast<const orbpl_camera*>(cam), scale, inv_sigma2, nlevels, out);
-  if (rc) return rc;
-  // Frame::mfLogScaleFactor (P15), as orbm_search_by_projection_kf takes it
-  *log_scale = nlevels > 1 ? (float)lsdm::log_((double)scale[1]) : 1.0f;
-  return ORBPL_OK;
-}
 
 bool orbpl::lsd_split_decision(int n_streams) {
   return split_on("ORBPL_LSD_SPLIT", n_streams, kLsdSplitMin);
 }
-
-extern "C" {
-
-int orbpl_frame_prepare(const orbpl_camera* cam, const orbpl_keypoint* kps, int n,
-                        const float* depth, orbpl_keypoint* kps_un, float* depth_out,
-                        float* uright_out, int32_t* grid_cell, float* bounds) {
-  if (!cam || n < 0 || (n > 0 && (!kps || !kps_un || !depth_out || !uright_out || !grid_cell)))
-    return arg_fail("bad argument");
-  TrackConsts c;
-  int rc = make_consts(cam, nullptr, nullptr, 1, &c);
-  if (rc) return rc;
-  if (bounds) { bounds[0] = c.minX; bounds[1] = c.maxX; bounds[2] = c.minY; bounds[3] = c.maxY; }
-  if (n == 0) return ORBPL_OK;
-  DBuf dk, dn, dd, dku, ddo, dur, dgc;
-  const size_t imgb = depth ? (size_t)cam->width * cam->height * 4 : 0;
-  HIP_CHECK(dk.alloc((size_t)n * sizeof(KeyPointD)));
-  HIP_CHECK(dn.alloc(4));
-  if (depth) HIP_CHECK(dd.alloc(imgb));
-  HIP_CHECK(dku.alloc((size_t)n * sizeof(KeyPointD)));
-  HIP_CHECK(ddo.alloc((size_t)n * 4));
-  HIP_CHECK(dur.alloc((size_t)n * 4));
-  HIP_CHECK(dgc.alloc((size_t)n * 4));
-  HIP_CHECK(hipMemcpy(dk.p, kps, (size_t)n * sizeof(KeyPointD), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dn.p, &n, 4, hipMemcpyHostToDevice));
-  if (depth) HIP_CHECK(hipMemcpy(dd.p, depth, imgb, hipMemcpyHostToDevice));
-  launch_frame_prepare(c, dk.as<KeyPointD>(), dn.as<int>(), n, depth ? dd.as<float>() : nullptr, 0,
-                       dku.as<KeyPointD>(), ddo.as<float>(), dur.as<float>(), dgc.as<int>(), 1,
-                       scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(kps_un, dku.p, (size_t)n * sizeof(KeyPointD), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(depth_out, ddo.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(uright_out, dur.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(grid_cell, dgc.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-int orbm_search_by_projection_last(const orbpl_camera* cam, const float* scale_factors, int nlevels,
-                                   const orbpl_match_current* cur, const orbpl_match_last* last,
-                                   float th, int mono, int check_orientation, int32_t* match,
-                                   int* nmatches) {
-  if (!cam || !scale_factors || !cur || !last || !match || !nmatches) return arg_fail("NULL argument");
-  const int n = cur->n, nl = last->n;
-  if (n < 0 || nl < 0 || n > kMatchMaxKp || nl > kMatchMaxKp)
-    return arg_fail("keypoint count exceeds the matcher capacity (2048)");
-  TrackConsts c;
-  int rc = make_consts(cam, scale_factors, nullptr, nlevels, &c);
-  if (rc) return rc;
-  const int P = std::max(1, std::max(n, nl));
-  DBuf d_cku, d_cdesc, d_cur, d_cg, d_cn, d_lku, d_lhas, d_lout, d_lxyz, d_ldesc, d_lnobs, d_ln, d_T,
-      d_match, d_nm;
-  HIP_CHECK(d_cku.alloc((size_t)P * sizeof(KeyPointD)));
-  HIP_CHECK(d_cdesc.alloc((size_t)P * 32));
-  HIP_CHECK(d_cur.alloc((size_t)P * 4));
-  HIP_CHECK(d_cg.alloc((size_t)P * 4));
-  HIP_CHECK(d_cn.alloc(4));
-  HIP_CHECK(d_lku.alloc((size_t)P * sizeof(KeyPointD)));
-  HIP_CHECK(d_lhas.alloc((size_t)P));
-  HIP_CHECK(d_lout.alloc((size_t)P));
-  HIP_CHECK(d_lxyz.alloc((size_t)P * 12));
-  HIP_CHECK(d_ldesc.alloc((size_t)P * 32));
-  HIP_CHECK(d_lnobs.alloc((size_t)P * 4));
-  HIP_CHECK(d_ln.alloc(4));
-  HIP_CHECK(d_T.alloc(32 * 4));
-  HIP_CHECK(d_match.alloc((size_t)P * 4));
-  HIP_CHECK(d_nm.alloc(4));
-  if (n) {
-    HIP_CHECK(hipMemcpy(d_cku.p, cur->kps_un, (size_t)n * sizeof(KeyPointD), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_cdesc.p, cur->desc, (size_t)n * 32, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_cur.p, cur->uright, (size_t)n * 4, hipMemcpyHostToDevice));
-  }
-  HIP_CHECK(hipMemcpy(d_cn.p, &n, 4, hipMemcpyHostToDevice));
-  if (nl) {
-    HIP_CHECK(hipMemcpy(d_lku.p, last->kps_un, (size_t)nl * sizeof(KeyPointD), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_lhas.p, last->has_mp, (size_t)nl, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_lout.p, last->outlier, (size_t)nl, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_lxyz.p, last->mp_xyz, (size_t)nl * 12, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_ldesc.p, last->mp_desc, (size_t)nl * 32, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_lnobs.p, last->mp_nobs, (size_t)nl * 4, hipMemcpyHostToDevice));
-  }
-  HIP_CHECK(hipMemcpy(d_ln.p, &nl, 4, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_T.as<float>(), cur->Tcw, 64, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_T.as<float>() + 16, last->Tcw, 64, hipMemcpyHostToDevice));
-  MatchLaunch m{};
-  m.cur_kps_un = d_cku.as<KeyPointD>();
-  m.cur_desc = d_cdesc.as<uint8_t>();
-  m.cur_uright = d_cur.as<float>();
-  m.cur_gcell = nullptr;  // computed on device from kps_un (PosInGrid)
-  m.cur_n = d_cn.as<int>();
-  m.last_kps_un = d_lku.as<KeyPointD>();
-  m.last_has_mp = d_lhas.as<uint8_t>();
-  m.last_outlier = d_lout.as<uint8_t>();
-  m.last_xyz = d_lxyz.as<float>();
-  m.last_desc = d_ldesc.as<uint8_t>();
-  m.last_nobs = d_lnobs.as<int>();
-  m.last_n = d_ln.as<int>();
-  m.kp_pitch = P;
-  m.Tcw = d_T.as<float>();
-  m.Tlw = d_T.as<float>() + 16;
-  m.pose_stride = 32;
-  m.match = d_match.as<int>();
-  m.nmatches = d_nm.as<int>();
-  m.nm_stride = 1;
-  m.th = th;
-  m.mono = mono;
-  m.check_ori = check_orientation;
-  m.retry = 0;
-  m.active = nullptr;
-  launch_match_last(c, m, 1, scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  if (n) HIP_CHECK(hipMemcpy(match, d_match.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(nmatches, d_nm.p, 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-int orbpl_pose_optimization(const orbpl_camera* cam, const orbpl_pose_problem* P, float* Tcw,
-                            uint8_t* outlier, uint8_t* line_outlier, int* n_inliers) {
-  return orbpl_pose_optimization_ex(cam, P, 0, Tcw, outlier, line_outlier, n_inliers);
-}
-
-int orbpl_pose_optimization_ex(const orbpl_camera* cam, const orbpl_pose_problem* P, int flags,
-                               float* Tcw, uint8_t* outlier, uint8_t* line_outlier,
-                               int* n_inliers) {
-  if (!cam || !P || !Tcw || !n_inliers) return arg_fail("NULL argument");
-  if (flags & ~ORBPL_POSE_FIXED_LINE_JAC) return arg_fail("unknown pose flag");
-  const int n = P->n, nl = P->nl;
-  if (n < 0 || nl < 0 || n + nl > kPoseMaxEdges) return arg_fail("too many edges (max 2304)");
-  if (n > 0 && (!P->kps_un || !P->uright || !P->has_mp || !P->mp_xyz || !outlier))
-    return arg_fail("NULL point arrays");
-  if (nl > 0 && (!P->kl_obs || !P->kl_octave || !P->has_ml || !P->ml_xyz || !line_outlier))
-    return arg_fail("NULL line arrays");
-  TrackConsts c;
-  int rc = make_consts(cam, nullptr, P->inv_sigma2, P->nlevels, &c);
-  if (rc) return rc;
-  const int Pn = std::max(1, n), Pl = std::max(1, nl);
-  DBuf d_ku, d_ur, d_has, d_xyz, d_n, d_klo, d_klv, d_hml, d_mlx, d_T, d_out, d_lout, d_nin, d_edges;
-  HIP_CHECK(d_ku.alloc((size_t)Pn * sizeof(KeyPointD)));
-  HIP_CHECK(d_ur.alloc((size_t)Pn * 4));
-  HIP_CHECK(d_has.alloc((size_t)Pn));
-  HIP_CHECK(d_xyz.alloc((size_t)Pn * 12));
-  HIP_CHECK(d_n.alloc(4));
-  HIP_CHECK(d_klo.alloc((size_t)Pl * 16));
-  HIP_CHECK(d_klv.alloc((size_t)Pl * 4));
-  HIP_CHECK(d_hml.alloc((size_t)Pl));
-  HIP_CHECK(d_mlx.alloc((size_t)Pl * 24));
-  HIP_CHECK(d_T.alloc(64));
-  HIP_CHECK(d_out.alloc((size_t)Pn));
-  HIP_CHECK(d_lout.alloc((size_t)Pl));
-  HIP_CHECK(d_nin.alloc(4));
-  HIP_CHECK(d_edges.alloc((size_t)kPoseMaxEdges * pose_edge_bytes()));
-  if (n) {
-    HIP_CHECK(hipMemcpy(d_ku.p, P->kps_un, (size_t)n * sizeof(KeyPointD), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_ur.p, P->uright, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_has.p, P->has_mp, (size_t)n, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_xyz.p, P->mp_xyz, (size_t)n * 12, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_out.p, outlier, (size_t)n, hipMemcpyHostToDevice));
-  }
-  if (nl) {
-    HIP_CHECK(hipMemcpy(d_klo.p, P->kl_obs, (size_t)nl * 16, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_klv.p, P->kl_octave, (size_t)nl * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_hml.p, P->has_ml, (size_t)nl, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_mlx.p, P->ml_xyz, (size_t)nl * 24, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_lout.p, line_outlier, (size_t)nl, hipMemcpyHostToDevice));
-  }
-  HIP_CHECK(hipMemcpy(d_n.p, &n, 4, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_T.p, Tcw, 64, hipMemcpyHostToDevice));
-  PoseLaunch p{};
-  p.kps_un = d_ku.as<KeyPointD>();
-  p.uright = d_ur.as<float>();
-  p.match = nullptr;
-  p.has_mp = d_has.as<uint8_t>();
-  p.mp_xyz = d_xyz.as<float>();
-  p.n = d_n.as<int>();
-  p.kp_pitch = Pn;
-  p.kl_obs = d_klo.as<float>();
-  p.kl_octave = d_klv.as<int>();
-  p.has_ml = d_hml.as<uint8_t>();
-  p.ml_xyz = d_mlx.as<float>();
-  p.nl = nl;
-  p.Tcw = d_T.as<float>();
-  p.pose_stride = 16;
-  p.outlier = d_out.as<uint8_t>();
-  p.line_outlier = d_lout.as<uint8_t>();
-  p.ninliers = d_nin.as<int>();
-  p.nm_stride = 1;
-  p.active = nullptr;
-  p.edges = reinterpret_cast<PoseEdge*>(d_edges.p);
-  p.fixed_line_jac = (flags & ORBPL_POSE_FIXED_LINE_JAC) ? 1 : 0;
-  launch_pose(c, p, 1, scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(Tcw, d_T.p, 64, hipMemcpyDeviceToHost));
-  if (n) HIP_CHECK(hipMemcpy(outlier, d_out.p, (size_t)n, hipMemcpyDeviceToHost));
-  if (nl) HIP_CHECK(hipMemcpy(line_outlier, d_lout.p, (size_t)nl, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(n_inliers, d_nin.p, 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-int orbpl_frame_is_in_frustum(const orbpl_camera* cam, float scale_factor, int nlevels,
-                              const float* Tcw, int n, const float* xyz, const float* normal,
-                              const float* min_dist, const float* max_dist, float view_cos_limit,
-                              uint8_t* in_view, float* proj_x, float* proj_y, float* proj_xr,
-                              int32_t* level, float* view_cos) {
-  if (!cam || !Tcw || n < 0 || nlevels < 1 || nlevels > kMaxLevelsT) return arg_fail("bad argument");
-  if (n > 0 && (!xyz || !normal || !min_dist || !max_dist || !in_view || !proj_x || !proj_y ||
-                !proj_xr || !level || !view_cos))
-    return arg_fail("NULL map point arrays");
-  TrackConsts c;
-  int rc = make_consts(cam, nullptr, nullptr, nlevels, &c);
-  if (rc) return rc;
-  if (n == 0) return ORBPL_OK;
-  // Frame::mfLogScaleFactor = log(mfScaleFactor) on a float (P15)
-  const float log_scale = (float)lsdm::log_((double)scale_factor);
-  DBuf dT, dx, dn, dmi, dma, div, dpx, dpy, dpr, dl, dvc;
-  HIP_CHECK(dT.alloc(64));
-  HIP_CHECK(dx.alloc((size_t)n * 12));
-  HIP_CHECK(dn.alloc((size_t)n * 12));
-  HIP_CHECK(dmi.alloc((size_t)n * 4));
-  HIP_CHECK(dma.alloc((size_t)n * 4));
-  HIP_CHECK(div.alloc(n));
-  HIP_CHECK(dpx.alloc((size_t)n * 4));
-  HIP_CHECK(dpy.alloc((size_t)n * 4));
-  HIP_CHECK(dpr.alloc((size_t)n * 4));
-  HIP_CHECK(dl.alloc((size_t)n * 4));
-  HIP_CHECK(dvc.alloc((size_t)n * 4));
-  HIP_CHECK(hipMemcpy(dT.p, Tcw, 64, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dx.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dn.p, normal, (size_t)n * 12, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dmi.p, min_dist, (size_t)n * 4, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dma.p, max_dist, (size_t)n * 4, hipMemcpyHostToDevice));
-  InFrustumArgs a{n, dT.as<float>(), dx.as<float>(), dn.as<float>(), dmi.as<float>(),
-                  dma.as<float>(), view_cos_limit, div.as<uint8_t>(), dpx.as<float>(),
-                  dpy.as<float>(), dpr.as<float>(), dl.as<int>(), dvc.as<float>()};
-  launch_in_frustum(c, log_scale, a, scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(in_view, div.p, n, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(proj_x, dpx.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(proj_y, dpy.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(proj_xr, dpr.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(level, dl.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(view_cos, dvc.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-int orbm_search_by_projection_local(const orbpl_camera* cam, const float* scale_factors,
-                                    int nlevels, const orbpl_match_current* cur, int nmp,
-                                    const uint8_t* in_view, const float* proj_x,
-                                    const float* proj_y, const float* proj_xr,
-                                    const int32_t* level, const float* view_cos,
-                                    const uint8_t* mp_desc, const int32_t* mp_nobs,
-                                    const int32_t* cur_nobs, float th, float nnratio,
-                                    int32_t* match, int* nmatches) {
-  if (!cam || !scale_factors || !cur || !nmatches || nmp < 0) return arg_fail("bad argument");
-  const int n = cur->n;
-  if (n < 0 || n > kMatchMaxKp) return arg_fail("keypoint count exceeds the matcher capacity (2048)");
-  if (n > 0 && (!cur->kps_un || !cur->desc || !cur->uright || !match)) return arg_fail("NULL frame arrays");
-  if (nmp > 0 && (!in_view || !proj_x || !proj_y || !proj_xr || !level || !view_cos || !mp_desc ||
-                  !mp_nobs))
-    return arg_fail("NULL map point arrays");
-  for (int i = 0; i < nmp; i++)
-    if (in_view[i] && (level[i] < 0 || level[i] >= nlevels)) return arg_fail("level out of range");
-  TrackConsts c;
-  int rc = make_consts(cam, scale_factors, nullptr, nlevels, &c);
-  if (rc) return rc;
-  const int P = std::max(1, n), M = std::max(1, nmp);
-  DBuf dku, dde, dur, dcn, div, dpx, dpy, dpr, dl, dvc, dmd, dmn, dm, dnm, dsc;
-  HIP_CHECK(dku.alloc((size_t)P * sizeof(KeyPointD)));
-  HIP_CHECK(dde.alloc((size_t)P * 32));
-  HIP_CHECK(dur.alloc((size_t)P * 4));
-  HIP_CHECK(dcn.alloc((size_t)P * 4));
-  HIP_CHECK(div.alloc(M));
-  HIP_CHECK(dpx.alloc((size_t)M * 4));
-  HIP_CHECK(dpy.alloc((size_t)M * 4));
-  HIP_CHECK(dpr.alloc((size_t)M * 4));
-  HIP_CHECK(dl.alloc((size_t)M * 4));
-  HIP_CHECK(dvc.alloc((size_t)M * 4));
-  HIP_CHECK(dmd.alloc((size_t)M * 32));
-  HIP_CHECK(dmn.alloc((size_t)M * 4));
-  HIP_CHECK(dm.alloc((size_t)P * 4));
-  HIP_CHECK(dnm.alloc(4));
-  HIP_CHECK(dsc.alloc((size_t)M * sizeof(int4)));
-  if (n) {
-    HIP_CHECK(hipMemcpy(dku.p, cur->kps_un, (size_t)n * sizeof(KeyPointD), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dde.p, cur->desc, (size_t)n * 32, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dur.p, cur->uright, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (cur_nobs) HIP_CHECK(hipMemcpy(dcn.p, cur_nobs, (size_t)n * 4, hipMemcpyHostToDevice));
-  }
-  if (nmp) {
-    HIP_CHECK(hipMemcpy(div.p, in_view, nmp, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dpx.p, proj_x, (size_t)nmp * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dpy.p, proj_y, (size_t)nmp * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dpr.p, proj_xr, (size_t)nmp * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dl.p, level, (size_t)nmp * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dvc.p, view_cos, (size_t)nmp * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dmd.p, mp_desc, (size_t)nmp * 32, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dmn.p, mp_nobs, (size_t)nmp * 4, hipMemcpyHostToDevice));
-  }
-  LocalArgs a{};
-  a.kps_un = dku.as<KeyPointD>();
-  a.desc = dde.as<uint8_t>();
-  a.uright = dur.as<float>();
-  a.n = n;
-  a.cur_nobs = cur_nobs ? dcn.as<int>() : nullptr;
-  a.nmp = nmp;
-  a.in_view = div.as<uint8_t>();
-  a.proj_x = dpx.as<float>();
-  a.proj_y = dpy.as<float>();
-  a.proj_xr = dpr.as<float>();
-  a.level = dl.as<int>();
-  a.view_cos = dvc.as<float>();
-  a.mp_desc = dmd.as<uint8_t>();
-  a.mp_nobs = dmn.as<int>();
-  a.th = th;
-  a.nnratio = nnratio;
-  a.match = dm.as<int>();
-  a.nmatches = dnm.as<int>();
-  a.scratch = dsc.as<int4>();
-  launch_match_local(c, a, scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  if (n) HIP_CHECK(hipMemcpy(match, dm.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(nmatches, dnm.p, 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-int orbpl_line_frame_prepare(const orbpl_camera* cam, const orbpl_keyline* kl, int n,
-                             const float* depth, orbpl_keyline* kl_un, float* dstart, float* dend,
-                             float* ur_start, float* ur_end) {
-  if (!cam || n < 0 || (n > 0 && (!kl || !kl_un || !dstart || !dend || !ur_start || !ur_end)))
-    return arg_fail("bad argument");
-  if (n > kLineKeep) return arg_fail("more key lines than LineExtractor keeps (80)");
-  TrackConsts c;
-  int rc = make_consts(cam, nullptr, nullptr, 1, &c);
-  if (rc) return rc;
-  if (n == 0) return ORBPL_OK;
-  DBuf dn, dkl, dku, dd, dds, dde, dus, due;
-  const size_t imgb = depth ? (size_t)cam->width * cam->height * 4 : 0;
-  HIP_CHECK(dn.alloc(4));
-  HIP_CHECK(dkl.alloc((size_t)kLineKeep * sizeof(orbpl_keyline)));
-  HIP_CHECK(dku.alloc((size_t)kLineKeep * sizeof(orbpl_keyline)));
-  if (depth) HIP_CHECK(dd.alloc(imgb));
-  HIP_CHECK(dds.alloc(kLineKeep * 4));
-  HIP_CHECK(dde.alloc(kLineKeep * 4));
-  HIP_CHECK(dus.alloc(kLineKeep * 4));
-  HIP_CHECK(due.alloc(kLineKeep * 4));
-  DBuf dlm, dlo;
-  HIP_CHECK(dlm.alloc(kLineKeep * 4));
-  HIP_CHECK(dlo.alloc(kLineKeep));
-  HIP_CHECK(hipMemcpy(dn.p, &n, 4, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dkl.p, kl, (size_t)n * sizeof(orbpl_keyline), hipMemcpyHostToDevice));
-  if (depth) HIP_CHECK(hipMemcpy(dd.p, depth, imgb, hipMemcpyHostToDevice));
-  LineTrackArgs a{};
-  a.nl = dn.as<int>();
-  a.kl = dkl.as<orbpl_keyline>();
-  a.kl_un = dku.as<orbpl_keyline>();
-  a.depth = depth ? dd.as<float>() : nullptr;
-  a.depth_pitch = 0;
-  a.dstart = dds.as<float>();
-  a.dend = dde.as<float>();
-  a.ur_start = dus.as<float>();
-  a.ur_end = due.as<float>();
-  a.lmatch = dlm.as<int>();
-  a.loutlier = dlo.as<uint8_t>();
-  launch_line_prepare(c, a, 1, scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(kl_un, dku.p, (size_t)n * sizeof(orbpl_keyline), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(dstart, dds.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(dend, dde.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(ur_start, dus.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(ur_end, due.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-int orbl_search_by_projection_last(const orbpl_camera* cam, const float* Tcw, int ncur,
-                                   const orbpl_keyline* cur_kl_un, const uint8_t* cur_desc,
-                                   int nlast, const orbpl_keyline* last_kl_un,
-                                   const uint8_t* has_ml, const uint8_t* last_outlier,
-                                   const float* ml_xyz6, const uint8_t* last_desc, int32_t* match,
-                                   int* nmatches) {
-  if (!cam || !Tcw || !nmatches || ncur < 0 || nlast < 0) return arg_fail("bad argument");
-  if (ncur > kLineKeep || nlast > kLineKeep)
-    return arg_fail("more key lines than LineExtractor keeps (80)");
-  if ((ncur > 0 && (!cur_kl_un || !cur_desc || !match)) ||
-      (nlast > 0 && (!last_kl_un || !has_ml || !last_outlier || !ml_xyz6 || !last_desc)))
-    return arg_fail("NULL line arrays");
-  TrackConsts c;
-  int rc = make_consts(cam, nullptr, nullptr, 1, &c);
-  if (rc) return rc;
-  const size_t L = kLineKeep;
-  DBuf dn, dln, dku, dde, dlk, dhm, dlo, dxyz, dld, dm, dst;
-  HIP_CHECK(dn.alloc(4));
-  HIP_CHECK(dln.alloc(4));
-  HIP_CHECK(dku.alloc(L * sizeof(orbpl_keyline)));
-  HIP_CHECK(dde.alloc(L * 32));
-  HIP_CHECK(dlk.alloc(L * sizeof(orbpl_keyline)));
-  HIP_CHECK(dhm.alloc(L));
-  HIP_CHECK(dlo.alloc(L));
-  HIP_CHECK(dxyz.alloc(L * 24));
-  HIP_CHECK(dld.alloc(L * 32));
-  HIP_CHECK(dm.alloc(L * 4));
-  HIP_CHECK(dst.alloc(sizeof(StreamState)));
-  StreamState st{};
-  memcpy(st.Tcw, Tcw, 64);
-  st.has_last = 1;
-  HIP_CHECK(hipMemcpy(dst.p, &st, sizeof(st), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dn.p, &ncur, 4, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dln.p, &nlast, 4, hipMemcpyHostToDevice));
-  if (ncur) {
-    HIP_CHECK(hipMemcpy(dku.p, cur_kl_un, ncur * sizeof(orbpl_keyline), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dde.p, cur_desc, (size_t)ncur * 32, hipMemcpyHostToDevice));
-  }
-  if (nlast) {
-    HIP_CHECK(hipMemcpy(dlk.p, last_kl_un, nlast * sizeof(orbpl_keyline), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dhm.p, has_ml, nlast, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dlo.p, last_outlier, nlast, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dxyz.p, ml_xyz6, (size_t)nlast * 24, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dld.p, last_desc, (size_t)nlast * 32, hipMemcpyHostToDevice));
-  }
-  LineTrackArgs a{};
-  a.nl = dn.as<int>();
-  a.kl_un = dku.as<orbpl_keyline>();
-  a.desc = dde.as<uint8_t>();
-  a.lmatch = dm.as<int>();
-  a.last_nl = dln.as<int>();
-  a.last_kl_un = dlk.as<orbpl_keyline>();
-  a.last_has_ml = dhm.as<uint8_t>();
-  a.last_loutlier = dlo.as<uint8_t>();
-  a.last_ml_xyz = dxyz.as<float>();
-  a.last_desc = dld.as<uint8_t>();
-  launch_line_match(c, a, dst.as<StreamState>(), 1, scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  if (ncur) HIP_CHECK(hipMemcpy(match, dm.p, (size_t)ncur * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(&st, dst.p, sizeof(st), hipMemcpyDeviceToHost));
-  *nmatches = st.nlmatches;
-  return ORBPL_OK;
-}
-
-int orbm_search_by_bow(int nkf, const int32_t* kf_node, const uint8_t* kf_valid,
-                       const uint8_t* kf_desc, const float* kf_angle, int nf, const int32_t* f_node,
-                       const uint8_t* f_desc, const float* f_angle, float nnratio, int check_ori,
-                       int32_t* match, int* nmatches) {
-  if (nkf < 0 || nf < 0 || !nmatches) return arg_fail("bad argument");
-  if (nkf > 2048 || nf > 2048) return arg_fail("more than 2048 features");
-  if ((nkf > 0 && (!kf_node || !kf_valid || !kf_desc || !kf_angle)) ||
-      (nf > 0 && (!f_node || !f_desc || !f_angle || !match)))
-    return arg_fail("NULL feature arrays");
-  for (int i = 0; i < nkf; i++)
-    if (kf_node[i] >= (1 << 21) - 1) return arg_fail("vocabulary node id >= 2^21 - 1");
-  for (int i = 0; i < nf; i++)
-    if (f_node[i] >= (1 << 21) - 1) return arg_fail("vocabulary node id >= 2^21 - 1");
-  const size_t K = std::max(1, nkf), F = std::max(1, nf);
-  DBuf dkn, dkv, dkd, dka, dfn, dfd, dfa, dm, dnm;
-  HIP_CHECK(dkn.alloc(K * 4));
-  HIP_CHECK(dkv.alloc(K));
-  HIP_CHECK(dkd.alloc(K * 32));
-  HIP_CHECK(dka.alloc(K * 4));
-  HIP_CHECK(dfn.alloc(F * 4));
-  HIP_CHECK(dfd.alloc(F * 32));
-  HIP_CHECK(dfa.alloc(F * 4));
-  HIP_CHECK(dm.alloc(F * 4));
-  HIP_CHECK(dnm.alloc(4));
-  if (nkf) {
-    HIP_CHECK(hipMemcpy(dkn.p, kf_node, K * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dkv.p, kf_valid, K, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dkd.p, kf_desc, K * 32, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dka.p, kf_angle, K * 4, hipMemcpyHostToDevice));
-  }
-  if (nf) {
-    HIP_CHECK(hipMemcpy(dfn.p, f_node, F * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dfd.p, f_desc, F * 32, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dfa.p, f_angle, F * 4, hipMemcpyHostToDevice));
-  }
-  BowArgs a{nkf, dkn.as<int>(), dkv.as<uint8_t>(), dkd.as<uint8_t>(), dka.as<float>(), nf,
-            dfn.as<int>(), dfd.as<uint8_t>(), dfa.as<float>(), nnratio, check_ori,
-            dm.as<int>(), dnm.as<int>()};
-  launch_match_bow(a, scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  if (nf) HIP_CHECK(hipMemcpy(match, dm.p, F * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(nmatches, dnm.p, 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-// Frame::mfLogScaleFactor = log(mfScaleFactor) (P15); mvScaleFactors[1] is
-// 1.0f * mfScaleFactor. One level: PredictScale always gives level 0.
-static float log_scale_of(const float* scale_factors, int nlevels) {
-  return nlevels > 1 ? (float)lsdm::log_((double)scale_factors[1]) : 1.0f;
-}
-
-int orbm_search_by_projection_kf_batch_device(const orbpl_camera* cam, const float* scale_factors,
-                                              int nlevels, const orbm_kf_device_batch* b,
-                                              int batch, float th, int orb_dist, int check_ori,
-                                              void* stream) {
-  if (!cam || !scale_factors || !b || batch < 0) return arg_fail("bad argument");
-  if (b->kp_pitch < 1 || b->kf_pitch < 1 || b->kp_pitch > kMatchMaxKp || b->kf_pitch > kMatchMaxKp)
-    return arg_fail("pitch outside [1, 2048] (the matcher capacity)");
-  if (!b->d_cur_n || !b->d_Tcw || !b->d_cur_kps_un || !b->d_cur_desc || !b->d_cur_has_mp ||
-      !b->d_kf_n || !b->d_kf_angle || !b->d_kf_valid || !b->d_kf_found || !b->d_mp_xyz ||
-      !b->d_mp_min_dist || !b->d_mp_max_dist || !b->d_mp_desc || !b->d_match || !b->d_nmatches)
-    return arg_fail("NULL device array");
-  TrackConsts c;
-  int rc = make_consts(cam, scale_factors, nullptr, nlevels, &c);
-  if (rc) return rc;
-  if (batch == 0) return ORBPL_OK;
-  MatchKfArgs a{};
-  a.cur_kps_un = reinterpret_cast<const KeyPointD*>(b->d_cur_kps_un);
-  a.cur_desc = b->d_cur_desc;
-  a.cur_has_mp = b->d_cur_has_mp;
-  a.cur_n = b->d_cur_n;
-  a.kp_pitch = b->kp_pitch;
-  a.kf_angle = b->d_kf_angle;
-  a.kf_valid = b->d_kf_valid;
-  a.kf_found = b->d_kf_found;
-  a.mp_xyz = b->d_mp_xyz;
-  a.mp_min_dist = b->d_mp_min_dist;
-  a.mp_max_dist = b->d_mp_max_dist;
-  a.mp_desc = b->d_mp_desc;
-  a.kf_n = b->d_kf_n;
-  a.kf_pitch = b->kf_pitch;
-  a.Tcw = b->d_Tcw;
-  a.pose_stride = 16;
-  a.match = b->d_match;
-  a.nmatches = b->d_nmatches;
-  a.nm_stride = 1;
-  a.th = th;
-  a.orb_dist = orb_dist;
-  a.check_ori = check_ori;
-  a.log_scale = log_scale_of(scale_factors, nlevels);
-  launch_match_kf(c, a, batch, (hipStream_t)stream);
-  HIP_CHECK(hipGetLastError());
-  return ORBPL_OK;
-}
-
-int orbm_search_by_projection_kf(const orbpl_camera* cam, const float* scale_factors, int nlevels,
-                                 const orbpl_match_current* cur, const uint8_t* cur_has_mp,
-                                 int nkf, const float* kf_angle, const uint8_t* kf_valid,
-                                 const uint8_t* kf_found, const float* mp_xyz,
-                                 const float* mp_min_dist, const float* mp_max_dist,
-                                 const uint8_t* mp_desc, float th, int orb_dist, int check_ori,
-                                 int32_t* match, int* nmatches) {
-  if (!cam || !scale_factors || !cur || !nmatches) return arg_fail("NULL argument");
-  const int n = cur->n;
-  if (n < 0 || nkf < 0 || n > kMatchMaxKp || nkf > kMatchMaxKp)
-    return arg_fail("keypoint count exceeds the matcher capacity (2048)");
-  if (!cur->Tcw || (n > 0 && (!cur->kps_un || !cur->desc || !cur_has_mp || !match)) ||
-      (nkf > 0 && (!kf_angle || !kf_valid || !kf_found || !mp_xyz || !mp_min_dist ||
-                   !mp_max_dist || !mp_desc)))
-    return arg_fail("NULL feature arrays");
-  const size_t N = std::max(1, n), K = std::max(1, nkf);
-  DBuf d_n, d_T, d_ku, d_cd, d_ch, d_kn, d_ka, d_kv, d_kf, d_x, d_mn, d_mx, d_md, d_m, d_nm;
-  HIP_CHECK(d_n.alloc(4));
-  HIP_CHECK(d_T.alloc(64));
-  HIP_CHECK(d_ku.alloc(N * sizeof(KeyPointD)));
-  HIP_CHECK(d_cd.alloc(N * 32));
-  HIP_CHECK(d_ch.alloc(N));
-  HIP_CHECK(d_kn.alloc(4));
-  HIP_CHECK(d_ka.alloc(K * 4));
-  HIP_CHECK(d_kv.alloc(K));
-  HIP_CHECK(d_kf.alloc(K));
-  HIP_CHECK(d_x.alloc(K * 12));
-  HIP_CHECK(d_mn.alloc(K * 4));
-  HIP_CHECK(d_mx.alloc(K * 4));
-  HIP_CHECK(d_md.alloc(K * 32));
-  HIP_CHECK(d_m.alloc(N * 4));
-  HIP_CHECK(d_nm.alloc(4));
-  HIP_CHECK(hipMemcpy(d_n.p, &n, 4, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_T.p, cur->Tcw, 64, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(d_kn.p, &nkf, 4, hipMemcpyHostToDevice));
-  if (n) {
-    HIP_CHECK(hipMemcpy(d_ku.p, cur->kps_un, (size_t)n * sizeof(KeyPointD), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_cd.p, cur->desc, (size_t)n * 32, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_ch.p, cur_has_mp, (size_t)n, hipMemcpyHostToDevice));
-  }
-  if (nkf) {
-    HIP_CHECK(hipMemcpy(d_ka.p, kf_angle, (size_t)nkf * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_kv.p, kf_valid, (size_t)nkf, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_kf.p, kf_found, (size_t)nkf, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_x.p, mp_xyz, (size_t)nkf * 12, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_mn.p, mp_min_dist, (size_t)nkf * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_mx.p, mp_max_dist, (size_t)nkf * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_md.p, mp_desc, (size_t)nkf * 32, hipMemcpyHostToDevice));
-  }
-  const orbm_kf_device_batch b{(int32_t)N, d_n.as<int32_t>(), d_T.as<float>(),
-                               d_ku.as<orbpl_keypoint>(), d_cd.as<uint8_t>(), d_ch.as<uint8_t>(),
-                               (int32_t)K, d_kn.as<int32_t>(), d_ka.as<float>(), d_kv.as<uint8_t>(),
-                               d_kf.as<uint8_t>(), d_x.as<float>(), d_mn.as<float>(),
-                               d_mx.as<float>(), d_md.as<uint8_t>(), d_m.as<int32_t>(),
-                               d_nm.as<int32_t>()};
-  int rc = orbm_search_by_projection_kf_batch_device(cam, scale_factors, nlevels, &b, 1, th,
-                                                     orb_dist, check_ori, scratch_stream());
-  if (rc) return rc;
-  if (n) HIP_CHECK(hipMemcpy(match, d_m.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(nmatches, d_nm.p, 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-int orbpl_stereo_matches(const orbpl_camera* cam, orbx_ctx* left, orbx_ctx* right, int frame,
-                         const orbpl_keypoint* kl, const uint8_t* dl, int n,
-                         const orbpl_keypoint* kr, const uint8_t* dr, int nr, float* uright,
-                         float* depth) {
-  if (!cam || !left || !right || n < 0 || nr < 0) return arg_fail("bad argument");
-  if (n > 4096 || nr > 4096) return arg_fail("more than 4096 keypoints");
-  if ((n > 0 && (!kl || !dl || !uright || !depth)) || (nr > 0 && (!kr || !dr)))
-    return arg_fail("NULL keypoint arrays");
-  const uint8_t *pl = nullptr, *pr = nullptr;
-  const OrbGeom *gl = nullptr, *gr = nullptr;
-  hipStream_t sl, sr;
-  int rc = orbx_device_pyramid(left, frame, &pl, &gl, &sl);
-  if (rc) return rc;
-  rc = orbx_device_pyramid(right, frame, &pr, &gr, &sr);
-  if (rc) return rc;
-  if (gl->nlevels != gr->nlevels || gl->W != gr->W || gl->H != gr->H || gl->nlevels > 8)
-    return arg_fail("left and right extractors differ");
-  if (gl->H > 1024) return arg_fail("image taller than 1024 rows");
-  if (n == 0) return ORBPL_OK;
-  HIP_CHECK(hipStreamSynchronize(sl));
-  HIP_CHECK(hipStreamSynchronize(sr));
-  const int cap = std::max(1, nr) * 20;
-  DBuf dkl, ddl, dkr, ddr, dur, ddp, dsad, dent, derr;
-  HIP_CHECK(dkl.alloc((size_t)n * sizeof(KeyPointD)));
-  HIP_CHECK(ddl.alloc((size_t)n * 32));
-  HIP_CHECK(dkr.alloc((size_t)std::max(1, nr) * sizeof(KeyPointD)));
-  HIP_CHECK(ddr.alloc((size_t)std::max(1, nr) * 32));
-  HIP_CHECK(dur.alloc((size_t)n * 4));
-  HIP_CHECK(ddp.alloc((size_t)n * 4));
-  HIP_CHECK(dsad.alloc((size_t)n * 4));
-  HIP_CHECK(dent.alloc((size_t)cap * 2));
-  HIP_CHECK(derr.alloc(4));
-  HIP_CHECK(hipMemset(derr.p, 0, 4));
-  HIP_CHECK(hipMemcpy(dkl.p, kl, (size_t)n * sizeof(KeyPointD), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(ddl.p, dl, (size_t)n * 32, hipMemcpyHostToDevice));
-  if (nr) {
-    HIP_CHECK(hipMemcpy(dkr.p, kr, (size_t)nr * sizeof(KeyPointD), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(ddr.p, dr, (size_t)nr * 32, hipMemcpyHostToDevice));
-  }
-  StereoArgs a{};
-  a.n = n;
-  a.kl = dkl.as<KeyPointD>();
-  a.dl = ddl.as<uint8_t>();
-  a.nr = nr;
-  a.kr = dkr.as<KeyPointD>();
-  a.dr = ddr.as<uint8_t>();
-  a.pyrL = pl;
-  a.pyrR = pr;
-  for (int l = 0; l < gl->nlevels; l++) {
-    a.lv[l] = gl->lv[l];
-    a.scale[l] = gl->lv[l].scale;
-    a.inv_scale[l] = 1.0f / gl->lv[l].scale;
-  }
-  a.nrows = gl->H;
-  a.mb = cam->bf / cam->fx;
-  a.mbf = cam->bf;
-  a.uright = dur.as<float>();
-  a.depth = ddp.as<float>();
-  a.sad = dsad.as<int>();
-  a.entries = dent.as<uint16_t>();
-  a.entry_cap = cap;
-  a.err = derr.as<int>();
-  launch_stereo(a, 1, scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  int err = 0;
-  HIP_CHECK(hipMemcpy(&err, derr.p, 4, hipMemcpyDeviceToHost));
-  if (err) return (arg_fail("stereo row band capacity exceeded"), ORBPL_ERR_OVERFLOW);
-  HIP_CHECK(hipMemcpy(uright, dur.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(depth, ddp.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-int orbl_frame_is_in_frustum(const float* Tcw, int n, const float* xyz6, uint8_t* in_view) {
-  if (!Tcw || n < 0 || (n > 0 && (!xyz6 || !in_view))) return arg_fail("bad argument");
-  if (n == 0) return ORBPL_OK;
-  DBuf dT, dx, dv;
-  HIP_CHECK(dT.alloc(64));
-  HIP_CHECK(dx.alloc((size_t)n * 24));
-  HIP_CHECK(dv.alloc(n));
-  HIP_CHECK(hipMemcpy(dT.p, Tcw, 64, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dx.p, xyz6, (size_t)n * 24, hipMemcpyHostToDevice));
-  launch_line_in_frustum(dT.as<float>(), n, dx.as<float>(), dv.as<uint8_t>(), scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(in_view, dv.p, n, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-int orbl_search_by_projection_list(const orbpl_camera* cam, const float* Tcw, int ncur,
-                                   const orbpl_keyline* cur_kl_un, const uint8_t* cur_desc,
-                                   const int32_t* cur_nobs, int nml, const uint8_t* valid,
-                                   const float* ml_xyz6, const uint8_t* ml_desc, int32_t* match,
-                                   int* nmatches, int* wiped) {
-  if (!cam || !Tcw || !nmatches || ncur < 0 || nml < 0) return arg_fail("bad argument");
-  if (ncur > kLineKeep) return arg_fail("more key lines than LineExtractor keeps (80)");
-  if ((ncur > 0 && (!cur_kl_un || !cur_desc || !match)) ||
-      (nml > 0 && (!valid || !ml_xyz6 || !ml_desc)))
-    return arg_fail("NULL line arrays");
-  TrackConsts c;
-  int rc = make_consts(cam, nullptr, nullptr, 1, &c);
-  if (rc) return rc;
-  const size_t L = kLineKeep, M = std::max(1, nml);
-  DBuf dT, dku, dde, dcn, dv, dx, dmd, dpk, dps, dm, dnm, dw;
-  HIP_CHECK(dT.alloc(64));
-  HIP_CHECK(dku.alloc(L * sizeof(orbpl_keyline)));
-  HIP_CHECK(dde.alloc(L * 32));
-  HIP_CHECK(dcn.alloc(L * 4));
-  HIP_CHECK(dv.alloc(M));
-  HIP_CHECK(dx.alloc(M * 24));
-  HIP_CHECK(dmd.alloc(M * 32));
-  HIP_CHECK(dpk.alloc(M * sizeof(orbpl_keyline)));
-  HIP_CHECK(dps.alloc(M * 4));
-  HIP_CHECK(dm.alloc(L * 4));
-  HIP_CHECK(dnm.alloc(4));
-  HIP_CHECK(dw.alloc(4));
-  HIP_CHECK(hipMemcpy(dT.p, Tcw, 64, hipMemcpyHostToDevice));
-  if (ncur) {
-    HIP_CHECK(hipMemcpy(dku.p, cur_kl_un, ncur * sizeof(orbpl_keyline), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dde.p, cur_desc, (size_t)ncur * 32, hipMemcpyHostToDevice));
-    if (cur_nobs) HIP_CHECK(hipMemcpy(dcn.p, cur_nobs, (size_t)ncur * 4, hipMemcpyHostToDevice));
-  }
-  if (nml) {
-    HIP_CHECK(hipMemcpy(dv.p, valid, nml, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dx.p, ml_xyz6, (size_t)nml * 24, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dmd.p, ml_desc, (size_t)nml * 32, hipMemcpyHostToDevice));
-  }
-  LineListArgs a{};
-  a.Tcw = dT.as<float>();
-  a.ncur = ncur;
-  a.cur_kl_un = dku.as<orbpl_keyline>();
-  a.cur_desc = dde.as<uint8_t>();
-  a.cur_nobs = cur_nobs ? dcn.as<int>() : nullptr;
-  a.nml = nml;
-  a.valid = dv.as<uint8_t>();
-  a.ml_xyz6 = dx.as<float>();
-  a.ml_desc = dmd.as<uint8_t>();
-  a.proj_kl = dpk.as<orbpl_keyline>();
-  a.proj_src = dps.as<int>();
-  a.match = dm.as<int>();
-  a.nmatches = dnm.as<int>();
-  a.wiped = dw.as<int>();
-  launch_line_match_list(c, a, scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  if (ncur) HIP_CHECK(hipMemcpy(match, dm.p, (size_t)ncur * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(nmatches, dnm.p, 4, hipMemcpyDeviceToHost));
-  if (wiped) HIP_CHECK(hipMemcpy(wiped, dw.p, 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-int orbl_search_by_projection_pairs(const orbpl_camera* cam, const float* Tcw, int mode, int ncur,
-                                    const orbpl_keyline* cur_kl_un, const uint8_t* cur_desc,
-                                    const int32_t* cur_nobs, int nml, const uint8_t* valid,
-                                    const orbpl_keyline* base_kl, const float* ml_xyz6,
-                                    const uint8_t* ml_desc, const int32_t* ml_nobs,
-                                    orbpl_keyline* proj_kl, int32_t* proj_src, int* nproj,
-                                    int32_t* pairs, int pair_cap, int* npairs, int32_t* match,
-                                    int* nmatches, int* wiped) {
-  if (!cam || !Tcw || !nmatches || !nproj || !npairs || !wiped || ncur < 0 || nml < 0 ||
-      pair_cap < 0 || (mode != 0 && mode != 1))
-    return arg_fail("bad argument");
-  if (ncur > kLineKeep) return arg_fail("more key lines than LineExtractor keeps (80)");
-  if ((ncur > 0 && (!cur_kl_un || !cur_desc || !match)) ||
-      (nml > 0 && (!valid || !ml_xyz6 || !ml_desc || !proj_kl || !proj_src)) ||
-      (pair_cap > 0 && !pairs))
-    return arg_fail("NULL line arrays");
-  TrackConsts c;
-  int rc = make_consts(cam, nullptr, nullptr, 1, &c);
-  if (rc) return rc;
-  const size_t L = kLineKeep, M = std::max(1, nml), words = (size_t)(nml + 31) / 32;
-  DBuf dT, dku, dde, dcn, dv, dbk, dx, dmd, dmn, dpk, dps, dnp, dok, dpr, dnpr, dm, dnm, dw;
-  HIP_CHECK(dT.alloc(64));
-  HIP_CHECK(dku.alloc(L * sizeof(orbpl_keyline)));
-  HIP_CHECK(dde.alloc(L * 32));
-  HIP_CHECK(dcn.alloc(L * 4));
-  HIP_CHECK(dv.alloc(M));
-  HIP_CHECK(dbk.alloc(M * sizeof(orbpl_keyline)));
-  HIP_CHECK(dx.alloc(M * 24));
-  HIP_CHECK(dmd.alloc(M * 32));
-  HIP_CHECK(dmn.alloc(M * 4));
-  HIP_CHECK(dpk.alloc(M * sizeof(orbpl_keyline)));
-  HIP_CHECK(dps.alloc(M * 4));
-  HIP_CHECK(dnp.alloc(4));
-  HIP_CHECK(dok.alloc(std::max<size_t>(1, L * words) * 4));
-  HIP_CHECK(dpr.alloc(std::max<size_t>(1, (size_t)pair_cap) * 8));
-  HIP_CHECK(dnpr.alloc(4));
-  HIP_CHECK(dm.alloc(L * 4));
-  HIP_CHECK(dnm.alloc(4));
-  HIP_CHECK(dw.alloc(4));
-  HIP_CHECK(hipMemcpy(dT.p, Tcw, 64, hipMemcpyHostToDevice));
-  if (ncur) {
-    HIP_CHECK(hipMemcpy(dku.p, cur_kl_un, ncur * sizeof(orbpl_keyline), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dde.p, cur_desc, (size_t)ncur * 32, hipMemcpyHostToDevice));
-    if (cur_nobs) HIP_CHECK(hipMemcpy(dcn.p, cur_nobs, (size_t)ncur * 4, hipMemcpyHostToDevice));
-  }
-  if (nml) {
-    HIP_CHECK(hipMemcpy(dv.p, valid, nml, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dx.p, ml_xyz6, (size_t)nml * 24, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dmd.p, ml_desc, (size_t)nml * 32, hipMemcpyHostToDevice));
-    if (base_kl)
-      HIP_CHECK(hipMemcpy(dbk.p, base_kl, (size_t)nml * sizeof(orbpl_keyline), hipMemcpyHostToDevice));
-    if (ml_nobs) HIP_CHECK(hipMemcpy(dmn.p, ml_nobs, (size_t)nml * 4, hipMemcpyHostToDevice));
-  }
-  LinePairArgs a{};
-  a.Tcw = dT.as<float>();
-  a.mode = mode;
-  a.ncur = ncur;
-  a.cur_kl_un = dku.as<orbpl_keyline>();
-  a.cur_desc = dde.as<uint8_t>();
-  a.cur_nobs = cur_nobs ? dcn.as<int>() : nullptr;
-  a.nml = nml;
-  a.valid = dv.as<uint8_t>();
-  a.base_kl = base_kl ? dbk.as<orbpl_keyline>() : nullptr;
-  a.ml_xyz6 = dx.as<float>();
-  a.ml_desc = dmd.as<uint8_t>();
-  a.ml_nobs = ml_nobs ? dmn.as<int>() : nullptr;
-  a.proj_kl = dpk.as<orbpl_keyline>();
-  a.proj_src = dps.as<int>();
-  a.nproj = dnp.as<int>();
-  a.okbits = dok.as<unsigned>();
-  a.pairs = dpr.as<int>();
-  a.pair_cap = pair_cap;
-  a.npairs = dnpr.as<int>();
-  a.match = dm.as<int>();
-  a.nmatches = dnm.as<int>();
-  a.wiped = dw.as<int>();
-  launch_line_pairs(c, a, scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  int np = 0, npr = 0;
-  HIP_CHECK(hipMemcpy(&np, dnp.p, 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(&npr, dnpr.p, 4, hipMemcpyDeviceToHost));
-  if (np) {
-    HIP_CHECK(hipMemcpy(proj_kl, dpk.p, (size_t)np * sizeof(orbpl_keyline), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(proj_src, dps.p, (size_t)np * 4, hipMemcpyDeviceToHost));
-  }
-  if (std::min(npr, pair_cap) > 0)
-    HIP_CHECK(hipMemcpy(pairs, dpr.p, (size_t)std::min(npr, pair_cap) * 8, hipMemcpyDeviceToHost));
-  if (ncur) HIP_CHECK(hipMemcpy(match, dm.p, (size_t)ncur * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(nmatches, dnm.p, 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(wiped, dw.p, 4, hipMemcpyDeviceToHost));
-  *nproj = np;
-  *npairs = npr;
-  return ORBPL_OK;
-}
-
-int orbl_match_bf_knn(int nq, const uint8_t* qdesc, int nt, const uint8_t* tdesc, int32_t* out,
-                      int* nmatches) {
-  if (nq < 0 || nt < 0 || !nmatches) return arg_fail("bad argument");
-  if (nq > 256) return arg_fail("more than 256 query descriptors");
-  if ((nq > 0 && !qdesc) || (nt > 0 && (!tdesc || !out))) return arg_fail("NULL descriptor arrays");
-  DBuf dq, dt, dout, dn;
-  HIP_CHECK(dq.alloc(std::max(1, nq) * 32));
-  HIP_CHECK(dt.alloc(std::max(1, nt) * 32));
-  HIP_CHECK(dout.alloc(std::max(1, nt) * 4));
-  HIP_CHECK(dn.alloc(4));
-  if (nq) HIP_CHECK(hipMemcpy(dq.p, qdesc, (size_t)nq * 32, hipMemcpyHostToDevice));
-  if (nt) HIP_CHECK(hipMemcpy(dt.p, tdesc, (size_t)nt * 32, hipMemcpyHostToDevice));
-  launch_line_bf_knn(nq, dq.as<uint8_t>(), nt, dt.as<uint8_t>(), dout.as<int>(), dn.as<int>(),
-                     scratch_stream());
-  HIP_CHECK(hipGetLastError());
-  if (nt) HIP_CHECK(hipMemcpy(out, dout.p, (size_t)nt * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(nmatches, dn.p, 4, hipMemcpyDeviceToHost));
-  return ORBPL_OK;
-}
-
-}  // extern "C"
 
 // ---------------------------------------------------------------------------
 // Batched tracker
@@ -1680,10 +750,10 @@ int orbpl_tracker_clear_velocity(orbpl_tracker* t, const uint8_t* mask) {
   if (t->cstream) HIP_CHECK(hipStreamSynchronize(t->cstream));
   HIP_CHECK(hipStreamSynchronize(t->stream));
   if (t->tstream) HIP_CHECK(hipStreamSynchronize(t->tstream));
-  DBuf d;
-  HIP_CHECK(d.alloc((size_t)t->S));
-  HIP_CHECK(hipMemcpy(d.p, mask, (size_t)t->S, hipMemcpyHostToDevice));
-  launch_clear_velocity(t->map ? t->ma.ms : nullptr, t->d_state, d.as<uint8_t>(), t->S, nullptr);
+  HostStage st;
+  const uint8_t* d_mask = st.in(mask, t->S, t->S);
+  if (st.rc()) return st.rc();
+  launch_clear_velocity(t->map ? t->ma.ms : nullptr, t->d_state, d_mask, t->S, nullptr);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipDeviceSynchronize());
   return ORBPL_OK;
@@ -1860,7 +930,7 @@ static int map_track(orbpl_tracker* t, FrameBufs& C, FrameBufs& L, const LineTra
   fa.n_arr = a.l_count;
   fa.pitch = a.lp;
   fa.pose_stride = pstride;
-  const float log_scale = (float)lsdm::log_((double)t->scale_factor);   // P15
+  const float log_scale = log_scale_of(t->scale_factor);
   launch_in_frustum(t->consts, log_scale, fa, ts, S);
   LocalArgs ml{};
   ml.kps_un = C.kps_un;
@@ -2321,7 +1391,7 @@ static int tracker_step(orbpl_tracker* t, const uint8_t* d_gray, const float* d_
     fa.n_arr = t->l_n;
     fa.pitch = t->lp;
     fa.pose_stride = pstride;
-    const float log_scale = (float)lsdm::log_((double)t->scale_factor);   // P15
+    const float log_scale = log_scale_of(t->scale_factor);
     launch_in_frustum(t->consts, log_scale, fa, ts, S);
     char* stb = reinterpret_cast<char*>(t->d_state);
     LocalArgs ma{};
