@@ -253,7 +253,9 @@ int orbm_search_by_projection_last(const orbpl_camera* cam, const float* scale_f
  * left / right images were extracted by `left` / `right` (batch frame
  * `frame`; their pyramids are the reference's mvImagePyramid): uRight and
  * depth per left keypoint (-1: none). kl / kr = mvKeys / mvKeysRight as
- * returned by orbx_extract. n, nr <= 4096, image height <= 1024. */
+ * returned by orbx_extract, octaves inside the extractors' 1 to 16 levels.
+ * n, nr <= 4096, image height <= 1024; the two extractors share size and
+ * level count. */
 int orbpl_stereo_matches(const orbpl_camera* cam, orbx_ctx* left, orbx_ctx* right, int frame,
                          const orbpl_keypoint* kl, const uint8_t* dl, int n,
                          const orbpl_keypoint* kr, const uint8_t* dr, int nr, float* uright,

@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(256) k_stereo(StereoArgs a) {
   __syncthreads();
   for (int iR = t; iR < nr; iR += 256) {
     const KeyPointD k = a_kr[iR];
-    const float r = 2.0f * a.scale[k.octave];
+    const float r = 2.0f * a.lv[k.octave].scale;
     const int maxr = (int)ceilf(k.y + r), minr = (int)floorf(k.y - r);
     for (int yi = max(minr, 0); yi <= min(maxr, nRows - 1); yi++) atomicAdd(&row_start[yi], 1);
   }
@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(256) k_stereo(StereoArgs a) {
   }
   for (int iR = t; iR < nr; iR += 256) {
     const KeyPointD k = a_kr[iR];
-    const float r = 2.0f * a.scale[k.octave];
+    const float r = 2.0f * a.lv[k.octave].scale;
     const int maxr = (int)ceilf(k.y + r), minr = (int)floorf(k.y - r);
     for (int yi = max(minr, 0); yi <= min(maxr, nRows - 1); yi++)
       a_entries[atomicAdd(&row_fill[yi], 1)] = (uint16_t)iR;
@@ -122,19 +122,19 @@ __global__ void __launch_bounds__(256) k_stereo(StereoArgs a) {
     }
     if (bestDist >= (100 + 50) / 2) continue;
     const float uR0 = a_kr[bestIdxR].x;
-    const float scaleFactor = a.inv_scale[levelL];
+    const StereoLevel& G = a.lv[levelL];
+    const float scaleFactor = G.inv_scale;
     const float scaleduL = roundf(kpL.x * scaleFactor);
     const float scaledvL = roundf(kpL.y * scaleFactor);
     const float scaleduR0 = roundf(uR0 * scaleFactor);
     const int w = 5, L = 5;
-    const LevelGeom& G = a.lv[levelL];
     const int cuL = (int)scaleduL, cvL = (int)scaledvL, cuR = (int)scaleduR0;
     const float iniu = scaleduR0 + L - w;
     const float endu = scaleduR0 + L + w + 1;
     if (iniu < 0 || endu >= G.w) continue;
     if (cvL - w < 0 || cvL + w >= G.h || cuL - w < 0 || cuL + w >= G.w || cuR - L - w < 0) continue;
-    const uint8_t* PL = a_pyrL + content_off(G, 0, 0);
-    const uint8_t* PR = a_pyrR + content_off(G, 0, 0);
+    const uint8_t* PL = a_pyrL + G.off;
+    const uint8_t* PR = a_pyrR + G.off;
     const int cL = PL[(long long)cvL * G.pitch + cuL];
     int sads[11];
 #pragma unroll
@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(256) k_stereo(StereoArgs a) {
       }
     const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
     if (deltaR < -1 || deltaR > 1) continue;
-    float bestuR = a.scale[levelL] * ((float)scaleduR0 + (float)bestincR + deltaR);
+    float bestuR = G.scale * ((float)scaleduR0 + (float)bestincR + deltaR);
     float disparity = (uL - bestuR);
     if (disparity >= minD && disparity < maxD) {
       if (disparity <= 0) {

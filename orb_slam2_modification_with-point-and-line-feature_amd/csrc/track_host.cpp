@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstring>
 
@@ -518,13 +519,29 @@ int orbpl_stereo_matches(const orbpl_camera* cam, orbx_ctx* left, orbx_ctx* righ
   if (rc) return rc;
   rc = orbx_device_pyramid(right, frame, &pr, &gr, &sr);
   if (rc) return rc;
-  if (gl->nlevels != gr->nlevels || gl->W != gr->W || gl->H != gr->H || gl->nlevels > 8)
+  if (gl->nlevels != gr->nlevels || gl->W != gr->W || gl->H != gr->H)
     return arg_fail("left and right extractors differ");
   if (gl->H > 1024) return arg_fail("image taller than 1024 rows");
   if (n == 0) return ORBPL_OK;
+  for (int i = 0; i < n; i++)
+    if (kl[i].octave < 0 || kl[i].octave >= gl->nlevels)
+      return arg_fail("keypoint octave outside the pyramid");
+  // the row-band scratch holds exactly the entries of these right keypoints:
+  // rows floor(y - 2s) .. ceil(y + 2s) inside the image, as k_stereo counts them
+  long long entries = 0;
+  for (int i = 0; i < nr; i++) {
+    if (kr[i].octave < 0 || kr[i].octave >= gl->nlevels)
+      return arg_fail("keypoint octave outside the pyramid");
+    const float r = 2.0f * gl->lv[kr[i].octave].scale;
+    const float hi = ceilf(kr[i].y + r), lo = floorf(kr[i].y - r);
+    if (!(hi >= 0.0f) || !(lo <= (float)(gl->H - 1))) continue;   // no row (or not a number)
+    const int maxr = hi > (float)(gl->H - 1) ? gl->H - 1 : (int)hi;
+    const int minr = lo < 0.0f ? 0 : (int)lo;
+    entries += maxr - minr + 1;
+  }
   HIP_CHECK(hipStreamSynchronize(sl));
   HIP_CHECK(hipStreamSynchronize(sr));
-  const int R = std::max(1, nr), cap = R * 20;
+  const int R = std::max(1, nr), cap = (int)std::max(1LL, entries);
   HostStage st;
   StereoArgs a{};
   a.n = n;
@@ -535,12 +552,7 @@ int orbpl_stereo_matches(const orbpl_camera* cam, orbx_ctx* left, orbx_ctx* righ
   a.dr = st.in(dr, 32 * nr, 32 * R);
   a.pyrL = pl;
   a.pyrR = pr;
-  for (int l = 0; l < gl->nlevels; l++) {
-    a.lv[l] = gl->lv[l];
-    a.scale[l] = gl->lv[l].scale;
-    a.inv_scale[l] = 1.0f / gl->lv[l].scale;
-  }
-  a.nrows = gl->H;
+  stereo_set_levels(a, *gl);
   a.mb = cam->bf / cam->fx;
   a.mbf = cam->bf;
   a.uright = st.out<float>(n);

@@ -310,6 +310,18 @@ struct BowArgs {
 void launch_match_bow(const BowArgs& a, hipStream_t s);
 
 // Frame::ComputeStereoMatches (stereo.hip).
+// What k_stereo reads of one pyramid level: 32 bytes instead of a LevelGeom,
+// so that the table holds every level an extractor can have (kMaxLevels) and
+// the kernel argument still shrinks.
+struct StereoLevel {
+  long long off;       // content_off(level, 0, 0) inside one frame's pyramid
+  int w, h;            // content size
+  int pitch;           // padded row pitch in bytes
+  float scale;         // mvScaleFactors[level]
+  float inv_scale;     // mvInvScaleFactors[level]
+  int pad;
+};
+
 struct StereoArgs {
   // Batched: frame f = blockIdx.x reads counts n_arr[f] / nr_arr[f] (or n /
   // nr when NULL), keypoint rows at f * kp_pitch (kl, dl, kr, dr, uright,
@@ -326,9 +338,7 @@ struct StereoArgs {
   const uint8_t* dr;
   const uint8_t* pyrL;           // one frame's padded pyramids (orbx layout)
   const uint8_t* pyrR;
-  LevelGeom lv[8];
-  float scale[8];
-  float inv_scale[8];
+  StereoLevel lv[kMaxLevels];
   int nrows;
   float mb, mbf;
   float* uright;                 // mvuRight (-1: none)
@@ -339,6 +349,17 @@ struct StereoArgs {
   int* err;
 };
 void launch_stereo(const StereoArgs& a, int batch, hipStream_t s);
+
+// The level table and row count of `a` from an extractor's geometry (1 to
+// kMaxLevels levels; the levels past g.nlevels stay zero).
+inline void stereo_set_levels(StereoArgs& a, const OrbGeom& g) {
+  static_assert(sizeof(a.lv) / sizeof(a.lv[0]) == kMaxLevels, "one entry per extractor level");
+  for (int l = 0; l < g.nlevels && l < kMaxLevels; l++) {
+    const LevelGeom& G = g.lv[l];
+    a.lv[l] = StereoLevel{content_off(G, 0, 0), G.w, G.h, G.pitch, G.scale, 1.0f / G.scale, 0};
+  }
+  a.nrows = g.H;
+}
 
 void launch_in_frustum(const TrackConsts& c, float log_scale, const InFrustumArgs& a,
                        hipStream_t s, int nstreams = 1);

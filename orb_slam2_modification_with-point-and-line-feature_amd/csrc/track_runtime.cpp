@@ -588,7 +588,9 @@ int orbpl_tracker_create_ex(const orbpl_orb_params* orb, const orbpl_camera* cam
     TA(t->trk_src, L * 4);
   }
   if (t->stereo) {
-    // a right keypoint spans at most 4 * scale + 2 <= 18 rows (8 levels of 1.2)
+    // a right keypoint at scale s enters ceil(y + 2s) - floor(y - 2s) + 1 <= 4s + 3
+    // rows: 20 per keypoint hold every pyramid whose top scale is at most 4.25
+    // (8 levels of 1.2: 3.58); a taller one can raise the step's error flag
     t->st_entry_cap = (int)K * 20;
     // test hook: a smaller row-band capacity forces the overflow path
     if (const char* e = getenv("ORBPL_STEREO_ENTRY_CAP")) {
@@ -1172,12 +1174,7 @@ static int tracker_step(orbpl_tracker* t, const uint8_t* d_gray, const float* d_
     a.dr = t->r_desc;
     a.pyrL = pl;
     a.pyrR = pr;
-    for (int l = 0; l < gl->nlevels; l++) {
-      a.lv[l] = gl->lv[l];
-      a.scale[l] = gl->lv[l].scale;
-      a.inv_scale[l] = 1.0f / gl->lv[l].scale;
-    }
-    a.nrows = gl->H;
+    stereo_set_levels(a, *gl);
     a.mb = t->consts.mb;
     a.mbf = t->consts.bf;
     a.uright = C.uright;

@@ -230,12 +230,20 @@ def stereo_pair(seed=0, cam_name="KITTI00"):
 
 
 @functools.lru_cache(maxsize=8)
-def stereo_sequence(n=3, seed=0, cam_name="KITTI00"):
+def stereo_sequence(n=3, seed=0, cam_name="KITTI00", width=None, height=None):
     """n rectified stereo pairs along a seeded trajectory (right camera at
-    +mb along the left camera's x axis): cfg, Twc list, [(left, right)]."""
+    +mb along the left camera's x axis): cfg, Twc list, [(left, right)].
+    width / height: the same camera cut down to a smaller frame (focal length,
+    principal point and bf scaled with the width, so the field of view and the
+    baseline mb = bf / fx stay)."""
     load_pkg()
     import orbpl.synth as synth
     cfg = dict(getattr(synth, cam_name))
+    if width is not None:
+        k = width / cfg["width"]
+        cfg.update(fx=cfg["fx"] * k, fy=cfg["fy"] * k, cx=cfg["cx"] * k,
+                   cy=cfg["cy"] * height / cfg["height"], bf=cfg["bf"] * k, width=width,
+                   height=height)
     room = synth.default_room(seed)
     traj = synth.trajectory(n, seed=seed)
     shift = np.eye(4)

@@ -385,3 +385,18 @@ def test_refused_before_any_device_call(name, case, change, message):
     rc = fn(*args)
     text = L.orbpl_last_error().decode()
     assert (rc, text) == (orbpl.ORBPL_ERR_ARG, message)
+
+
+def test_stereo_tracker_refuses_more_than_1024_rows():
+    """k_stereo's row table holds 1024 rows: a stereo tracker for a taller
+    image is refused at creation, before any device call. The level count needs no refusal of its own: the stereo level table holds the
+    extractor's 16 (orbx_create refuses 17 for every tracker)."""
+    L = orbpl.lib()
+    p = orbpl.OrbParams(500, 1.1, 12, 20, 7)
+    tall = orbpl.Camera(525.0, 525.0, 319.5, 239.5, 0.0, 0.0, 0.0, 0.0, 0.0, 40.0, 3.0, 640, 1025)
+    h = C.c_void_p()
+    rc = L.orbpl_tracker_create_ex(C.byref(p), C.byref(tall), 1, 0, orbpl.Tracker.TRACK_STEREO,
+                                   C.byref(h))
+    assert (rc, L.orbpl_last_error().decode()) == (
+        orbpl.ORBPL_ERR_ARG, "stereo tracking supports images up to 1024 rows")
+    assert not h.value
