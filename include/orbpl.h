@@ -844,6 +844,178 @@ int orbl_search_for_triangulation(int nl1, const uint8_t* ldesc1, int nl2, const
                                   int32_t* pairs, int* npairs);
 
 /* ------------------------------------------------------------------------
+ * LocalMapping::SearchInNeighbors() (LocalMapping.cc:922-1103, the point
+ * half; the line half is commented out in the reference), non-monocular
+ * (nn = 10), with ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:
+ * 1107-1277), MapPoint::Replace (MapPoint.cc:177-229) and
+ * KeyFrame::UpdateConnections of the current keyframe, for many independent
+ * maps in one launch. The call mutates the map it is
+ * given. Not called by orbpl_tracker_step (P23 stays).
+ * ---------------------------------------------------------------------- */
+#define ORBLM_MAX_MAP_KF 64        /* keyframes of one map (the map model's bound) */
+#define ORBLM_MAX_TARGETS 60       /* 10 first neighbours + 5 second each */
+/* ORBmatcher::Fuse: the branch that ended a list entry's iteration */
+#define ORBM_FUSE_NULL 0           /* !pMP                                    */
+#define ORBM_FUSE_BAD 1            /* pMP->isBad()                            */
+#define ORBM_FUSE_IN_KF 2          /* pMP->IsInKeyFrame(pKF)                  */
+#define ORBM_FUSE_BEHIND 3         /* z < 0                                   */
+#define ORBM_FUSE_OUT_OF_IMAGE 4   /* !pKF->IsInImage(u, v)                   */
+#define ORBM_FUSE_DISTANCE 5       /* outside [0.8 min, 1.2 max]              */
+#define ORBM_FUSE_VIEW 6           /* PO.dot(Pn) < 0.5 * dist3D               */
+#define ORBM_FUSE_EMPTY_WINDOW 7   /* GetFeaturesInArea returned nothing      */
+#define ORBM_FUSE_NO_MATCH 8       /* bestDist > TH_LOW after the gates       */
+#define ORBM_FUSE_ADDED 9          /* AddObservation + AddMapPoint            */
+#define ORBM_FUSE_REPLACED 10      /* pMP->Replace(pMPinKF): the keyframe's point survives */
+#define ORBM_FUSE_REPLACES 11      /* pMPinKF->Replace(pMP): the projected point survives  */
+#define ORBM_FUSE_BAD_SLOT 12      /* the keypoint holds a bad point: counted, nothing done */
+/* A keyframe of a map: mnId (distinct within a map; observation order, P24),
+ * Tcw, n <= ORBLM_MAX_KEYPOINTS features (mvKeysUn, mvuRight, descriptors),
+ * mp[n] = the map point in each feature's slot as an index into the map's
+ * points (-1 none; in/out), ordered = its covisible keyframes in
+ * UpdateBestCovisibles order as indices into the map's keyframe table, ended
+ * by -1 or by its 64th entry (NULL = none; only the first 10 / 5 are read). */
+typedef struct orblm_map_keyframe {
+  int32_t id;
+  const float* Tcw;
+  int32_t n;
+  const orbpl_keypoint* kps_un;
+  const float* uright;
+  const uint8_t* desc;
+  int32_t* mp;
+  const int32_t* ordered;
+} orblm_map_keyframe;
+/* A map: nkf <= 64 keyframes and M <= 64 * 2048 map points. In/out per point:
+ * xyz[3], normal[3], min_dist / max_dist (the raw mfMinDistance /
+ * mfMaxDistance), desc[32], ref_kf (mpRefKF as a table index), bad,
+ * n_visible, n_found. The observations are derived from the slot arrays at
+ * entry. Out per point: replaced_by (mpReplaced, -1 none), n_obs
+ * (Observations()), obs[64] (the feature index in each keyframe of the table,
+ * -1 none), desc_src[2] = the (keyframe, feature) whose descriptor the point
+ * took when the call last recomputed it (-1, -1: not recomputed). A replaced
+ * point keeps its own n_visible / n_found, the survivor gains them. */
+typedef struct orblm_map {
+  int32_t nkf;
+  orblm_map_keyframe* kf;
+  int32_t M;
+  float* xyz;
+  float* normal;
+  float* min_dist;
+  float* max_dist;
+  uint8_t* desc;
+  int32_t* ref_kf;
+  uint8_t* bad;
+  int32_t* n_visible;
+  int32_t* n_found;
+  int32_t* replaced_by;
+  int32_t* n_obs;
+  int16_t* obs;
+  int32_t* desc_src;
+} orblm_map;
+/* What SearchInNeighbors reports besides the map: vpTargetKFs as built
+ * (duplicates kept), nFused of each forward Fuse and then of the backward one
+ * (n_fused[n_targets]), the size of vpFuseCandidates, and the current
+ * keyframe's UpdateConnections: conn_w[k] = KFcounter of table keyframe k,
+ * ordered / ordered_w = mvpOrderedConnectedKeyFrames / mvOrderedWeights
+ * (n_ordered entries; -1 = KFcounter was empty and the lists stay as they
+ * were), add_conn[k] = the weight keyframe k receives through AddConnection
+ * (0 none); the other keyframes' own lists are not updated (reported only). */
+typedef struct orblm_sin_result {
+  int32_t targets[ORBLM_MAX_TARGETS];
+  int32_t n_targets;
+  int32_t n_fused[ORBLM_MAX_TARGETS + 1];
+  int32_t n_candidates;
+  int32_t conn_w[ORBLM_MAX_MAP_KF];
+  int32_t ordered[ORBLM_MAX_MAP_KF];
+  int32_t ordered_w[ORBLM_MAX_MAP_KF];
+  int32_t n_ordered;
+  int32_t add_conn[ORBLM_MAX_MAP_KF];
+} orblm_sin_result;
+typedef struct orblm_sin_problem {
+  orblm_map map;
+  int32_t cur;              /* mpCurrentKeyFrame as a table index */
+  orblm_sin_result result;  /* out */
+} orblm_sin_problem;
+/* n problems, host pointers, one launch. ORBPL_ERR_ARG before any device
+ * call: NULL arrays, nkf outside [1, 64], more than 2048 features in a
+ * keyframe, M outside [0, 64 * 2048], two keyframes of a map with one id, an
+ * octave outside [0, nlevels), a slot index outside [-1, M), a point that sits
+ * twice in one keyframe, a good point whose ref_kf does not observe it, an
+ * ordered entry outside the table or naming its own keyframe, nlevels outside
+ * [1, 16], and an array that two problems of the call share (each keyframe
+ * and each point belongs to exactly one problem: the call writes them). */
+int orblm_search_in_neighbors(const orbpl_camera* cam, const float* scale_factors,
+                              const float* level_sigma2, int nlevels,
+                              orblm_sin_problem* problems, int n);
+/* The same over pools in device memory. Problem p owns the keyframes
+ * [kf0, kf0 + nkf) and the points [mp0, mp0 + nmp) of the pools, d_prob[5 * p
+ * ..] = (kf0, nkf, mp0, nmp, cur); slot, ordered, ref_kf, replaced_by and
+ * cur are indices relative to the problem's own range. The ranges of two
+ * problems of one call must not overlap: every problem writes its own. Per
+ * keyframe g: d_kf_id[g], d_kf_n[g], d_kf_Tcw[16 g], features at g * kp_pitch
+ * of d_kps_un / d_uright / d_desc (32 B rows, 16-byte aligned) / d_mp,
+ * d_ordered[64 g ..]. Per point m: d_xyz[3 m], d_normal[3 m], d_min_dist,
+ * d_max_dist, d_mp_desc[32 m], d_ref_kf, d_bad, d_n_visible, d_n_found
+ * (in/out); d_replaced_by, d_n_obs, d_obs[64 m], d_desc_src[2 m] (out),
+ * d_mark[m] (scratch). Per problem: d_result[p], and list_pitch entries each of
+ * the scratch d_list / d_search (list_pitch >= kp_pitch; a backward candidate
+ * list longer than list_pitch is cut there and sets *d_err, which the caller
+ * zeroes beforehand and which the host entry turns into ORBPL_ERR_OVERFLOW).
+ * Asynchronous on `stream`, no readback. Counts above a pitch and indices
+ * outside a problem's range are clamped / skipped on the device. */
+typedef struct orblm_sin_device_batch {
+  int32_t nkf, kp_pitch, nmp, list_pitch;
+  const int32_t* d_prob;
+  const int32_t* d_kf_id;
+  const int32_t* d_kf_n;
+  const float* d_kf_Tcw;
+  const orbpl_keypoint* d_kps_un;
+  const float* d_uright;
+  const uint8_t* d_desc;
+  int32_t* d_mp;
+  const int32_t* d_ordered;
+  float* d_xyz;
+  float* d_normal;
+  float* d_min_dist;
+  float* d_max_dist;
+  uint8_t* d_mp_desc;
+  int32_t* d_ref_kf;
+  uint8_t* d_bad;
+  int32_t* d_n_visible;
+  int32_t* d_n_found;
+  int32_t* d_replaced_by;
+  int32_t* d_n_obs;
+  int16_t* d_obs;
+  int32_t* d_desc_src;
+  uint8_t* d_mark;
+  orblm_sin_result* d_result;
+  int32_t* d_list;
+  int32_t* d_search;
+  int32_t* d_err;
+} orblm_sin_device_batch;
+int orblm_search_in_neighbors_batch_device(const orbpl_camera* cam, const float* scale_factors,
+                                           const float* level_sigma2, int nlevels,
+                                           const orblm_sin_device_batch* b, int n, void* stream);
+/* Profiling: the same launch with in-kernel time stamps. d_ticks (device, 3
+ * per problem): the time spent in the search phases of all Fuse calls, in
+ * their commit phases, and in the whole workgroup, in ticks of the 100 MHz
+ * constant clock. The stamps add a few instructions per Fuse call. */
+int orblm_debug_search_in_neighbors_phases(const orbpl_camera* cam, const float* scale_factors,
+                                           const float* level_sigma2, int nlevels,
+                                           const orblm_sin_device_batch* b, int n, void* stream,
+                                           long long* d_ticks);
+/* ORBmatcher::Fuse(pKF, vpMapPoints, th) alone on such a map: keyframe `kf`
+ * of the table and a list of n_list point indices (-1 = a null entry; an entry
+ * may repeat). The map is updated in place as above. Per list entry: reason
+ * (ORBM_FUSE_*), and where the search ran to its end (NO_MATCH, ADDED,
+ * REPLACED, REPLACES, BAD_SLOT) best_idx / best_dist (-1 / 256 when no
+ * candidate passed the gates), else -1 / 256. The one-call case of the same
+ * kernel. Refusals as orblm_search_in_neighbors, and list entries outside
+ * [-1, M). */
+int orbm_fuse(const orbpl_camera* cam, const float* scale_factors, const float* level_sigma2,
+              int nlevels, orblm_map* map, int kf, const int32_t* list, int n_list, float th,
+              int* n_fused, int32_t* best_idx, int32_t* best_dist, int32_t* reason);
+
+/* ------------------------------------------------------------------------
  * Optimizer::PoseOptimization / PoseOptimizationWithLines
  * (Optimizer.cc:375-619, 2132-2486): 4 rounds x 10 Levenberg-Marquardt
  * iterations on one SE3 vertex, Huber kernel in rounds 0-2, chi2 outlier

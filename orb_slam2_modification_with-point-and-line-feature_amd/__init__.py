@@ -2220,3 +2220,261 @@ class LmDeviceProblems:
         lpairs = b["lpairs"].download(np.int32, (S, NB))
         return [_lm_outputs(self.n1[s], self.nl1[s], int(npts[s]), pts[s], rec[s], pairs[s],
                             int(nlns[s]), lns[s], lrec[s], lpairs[s]) for s in range(self.ns)]
+
+
+# ---------------------------------------------------------------------------
+# LocalMapping::SearchInNeighbors with ORBmatcher::Fuse as one batched call
+# 
+# ---------------------------------------------------------------------------
+LM_MAX_MAP_KF, LM_MAX_TARGETS = 64, 60
+FUSE_REASONS = ("null", "bad", "in_kf", "behind", "out_of_image", "distance", "view",
+                "empty_window", "no_match", "added", "replaced", "replaces", "bad_slot")
+_SIN_POINT_IO = (("xyz", np.float32, 3), ("normal", np.float32, 3), ("min_dist", np.float32, 1),
+                 ("max_dist", np.float32, 1), ("desc", np.uint8, 32), ("ref_kf", np.int32, 1),
+                 ("bad", np.uint8, 1), ("n_visible", np.int32, 1), ("n_found", np.int32, 1))
+_SIN_POINT_OUT = (("replaced_by", np.int32, 1), ("n_obs", np.int32, 1),
+                  ("obs", np.int16, LM_MAX_MAP_KF), ("desc_src", np.int32, 2))
+
+
+class LmMapKeyFrame(C.Structure):
+    """orblm_map_keyframe"""
+    _fields_ = ([("id", C.c_int32), ("Tcw", C.c_void_p), ("n", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("kps_un", "uright", "desc", "mp", "ordered")])
+
+
+class LmMap(C.Structure):
+    """orblm_map"""
+    _fields_ = ([("nkf", C.c_int32), ("kf", C.c_void_p), ("M", C.c_int32)] +
+                [(k, C.c_void_p) for k, _, _ in _SIN_POINT_IO + _SIN_POINT_OUT])
+
+
+class LmSinResult(C.Structure):
+    """orblm_sin_result"""
+    _fields_ = [("targets", C.c_int32 * LM_MAX_TARGETS), ("n_targets", C.c_int32),
+                ("n_fused", C.c_int32 * (LM_MAX_TARGETS + 1)), ("n_candidates", C.c_int32),
+                ("conn_w", C.c_int32 * LM_MAX_MAP_KF), ("ordered", C.c_int32 * LM_MAX_MAP_KF),
+                ("ordered_w", C.c_int32 * LM_MAX_MAP_KF), ("n_ordered", C.c_int32),
+                ("add_conn", C.c_int32 * LM_MAX_MAP_KF)]
+
+
+class LmSinProblem(C.Structure):
+    """orblm_sin_problem"""
+    _fields_ = [("map", LmMap), ("cur", C.c_int32), ("result", LmSinResult)]
+
+
+class LmSinDeviceBatch(C.Structure):
+    """orblm_sin_device_batch: pools of keyframes and map points (see include/orbpl.h)"""
+    _fields_ = ([(k, C.c_int32) for k in ("nkf", "kp_pitch", "nmp", "list_pitch")] +
+                [(k, C.c_void_p) for k in (
+                    "d_prob", "d_kf_id", "d_kf_n", "d_kf_Tcw", "d_kps_un", "d_uright", "d_desc",
+                    "d_mp", "d_ordered", "d_xyz", "d_normal", "d_min_dist", "d_max_dist",
+                    "d_mp_desc", "d_ref_kf", "d_bad", "d_n_visible", "d_n_found", "d_replaced_by",
+                    "d_n_obs", "d_obs", "d_desc_src", "d_mark", "d_result", "d_list", "d_search",
+                    "d_err")])
+
+
+def _declare_fuse(L):
+    vp, i = C.c_void_p, C.c_int
+    L.orblm_search_in_neighbors.argtypes = [vp, vp, vp, i, vp, i]
+    L.orblm_search_in_neighbors_batch_device.argtypes = [vp, vp, vp, i, vp, i, vp]
+    L.orbm_fuse.argtypes = [vp, vp, vp, i, vp, i, vp, i, C.c_float, C.POINTER(C.c_int), vp, vp, vp]
+    L.orblm_debug_search_in_neighbors_phases.argtypes = [vp, vp, vp, i, vp, i, vp, vp]
+
+
+_declare_before_fuse = _declare
+
+
+def _declare(L):  # noqa: F811
+    _declare_before_fuse(L)
+    _declare_fuse(L)
+
+
+def _sin_ordered(kf):
+    o = [int(x) for x in kf.get("ordered", ())][:LM_MAX_MAP_KF]
+    return np.array(o + [-1] * (LM_MAX_MAP_KF - len(o)), np.int32)
+
+
+def _sin_map_arrays(m):
+    """copies of a map dict's arrays (the call writes them): per keyframe
+    (Tcw, kps_un, uright, desc, mp, ordered), per point the in/out and out arrays"""
+    kfs = []
+    for kf in m["kfs"]:
+        n = len(np.asarray(kf["uright"]))
+        kfs.append(dict(id=int(kf["id"]), n=n, Tcw=_c(kf["Tcw"], np.float32).reshape(16).copy(),
+                        kps_un=_c(kf["kps_un"], KP_DTYPE), uright=_c(kf["uright"], np.float32),
+                        desc=_c(kf["desc"], np.uint8).reshape(n, 32),
+                        mp=np.array(kf["mp"], np.int32).reshape(n), ordered=_sin_ordered(kf)))
+    M = len(np.asarray(m["bad"]))
+    pts = {}
+    for name, dt, w in _SIN_POINT_IO:
+        pts[name] = np.array(m[name], dt).reshape((M, w) if w > 1 else (M,))
+    for name, dt, w in _SIN_POINT_OUT:
+        pts[name] = np.full((M, w) if w > 1 else (M,), -1, dt)
+    return kfs, M, pts
+
+
+def _sin_map_struct(m, keep):
+    kfs, M, pts = _sin_map_arrays(m)
+    tab = (LmMapKeyFrame * max(1, len(kfs)))(*[
+        LmMapKeyFrame(k["id"], _ptr(k["Tcw"]), k["n"], _ptr(k["kps_un"]), _ptr(k["uright"]),
+                      _ptr(k["desc"]), _ptr(k["mp"]), _ptr(k["ordered"])) for k in kfs])
+    keep += [kfs, pts, tab]
+    s = LmMap(len(kfs), C.cast(tab, C.c_void_p), M,
+              *[_ptr(pts[name]) for name, _, _ in _SIN_POINT_IO + _SIN_POINT_OUT])
+    return s, kfs, pts
+
+
+def _sin_map_out(kfs, pts):
+    out = {k: v for k, v in pts.items()}
+    out["mp"] = [k["mp"] for k in kfs]
+    return out
+
+
+def _sin_result_out(out, r):
+    nt = r.n_targets
+    out.update(targets=np.array(r.targets[:nt], np.int32), n_fused=np.array(r.n_fused[:nt + 1], np.int32),
+               n_candidates=int(r.n_candidates), conn_w=np.array(r.conn_w, np.int32),
+               n_ordered=int(r.n_ordered), ordered=np.array(r.ordered[:max(0, r.n_ordered)], np.int32),
+               ordered_w=np.array(r.ordered_w[:max(0, r.n_ordered)], np.int32),
+               add_conn=np.array(r.add_conn, np.int32))
+    return out
+
+
+class NeighborFuser:
+    """LocalMapping::SearchInNeighbors (non-monocular, the point half) for many
+    independent maps in one launch, and ORBmatcher::Fuse alone. A problem is
+    dict(map=map, cur=index of the current keyframe); a map is dict(kfs=[keyframe],
+    xyz, normal, min_dist, max_dist, desc, ref_kf, bad, n_visible, n_found), a
+    keyframe dict(id, Tcw, kps_un, uright, desc, mp, ordered) with mp the map point
+    index per feature (-1 none) and ordered its covisible keyframes as indices into
+    kfs. The inputs are not modified: a result holds the updated arrays (mp as a
+    list per keyframe) plus replaced_by, n_obs, obs, desc_src and, for
+    search_in_neighbors, targets, n_fused, n_candidates, conn_w, ordered,
+    ordered_w, n_ordered, add_conn."""
+
+    def __init__(self, camera, scale_factors, level_sigma2):
+        self.camera = camera
+        self.scale = _c(scale_factors, np.float32)
+        self.sigma2 = _c(level_sigma2, np.float32)
+        assert len(self.scale) == len(self.sigma2)
+
+    def _consts(self):
+        return C.byref(self.camera), _ptr(self.scale), _ptr(self.sigma2), len(self.scale)
+
+    def search_in_neighbors(self, problems):
+        keep, P, parts = [], (LmSinProblem * max(1, len(problems)))(), []
+        for p, prob in enumerate(problems):
+            P[p].map, kfs, pts = _sin_map_struct(prob["map"], keep)
+            P[p].cur = int(prob["cur"])
+            parts.append((kfs, pts))
+        check(lib().orblm_search_in_neighbors(*self._consts(), P, len(problems)),
+              "orblm_search_in_neighbors")
+        return [_sin_result_out(_sin_map_out(*parts[p]), P[p].result) for p in range(len(problems))]
+
+    def fuse(self, map_, kf, points, th=3.0):
+        """ORBmatcher::Fuse(keyframe kf, points, th): (nFused, result) with
+        best_idx, best_dist and reason per list entry."""
+        keep = []
+        s, kfs, pts = _sin_map_struct(map_, keep)
+        lst = np.array(points, np.int32).reshape(-1)
+        n = len(lst)
+        bi, bd, rs = (np.zeros(max(1, n), np.int32) for _ in range(3))
+        nf = C.c_int(0)
+        check(lib().orbm_fuse(*self._consts(), C.byref(s), int(kf), _ptr(lst), n, float(th),
+                              C.byref(nf), _ptr(bi), _ptr(bd), _ptr(rs)), "orbm_fuse")
+        out = _sin_map_out(kfs, pts)
+        out.update(best_idx=bi[:n].copy(), best_dist=bd[:n].copy(), reason=rs[:n].copy())
+        return nf.value, out
+
+
+def fuse(camera, scale_factors, level_sigma2, map_, kf, points, th=3.0):
+    """NeighborFuser(camera, scale_factors, level_sigma2).fuse"""
+    return NeighborFuser(camera, scale_factors, level_sigma2).fuse(map_, kf, points, th)
+
+
+class SinDeviceProblems:
+    """The device pools of orblm_search_in_neighbors_batch_device for a list of
+    problems (as NeighborFuser.search_in_neighbors takes them): run() launches
+    without a host round trip, download() synchronises and returns the same
+    per-problem results. Every problem owns its range of the pools. A run
+    mutates the pools: upload() restores the inputs."""
+
+    def __init__(self, fuser, problems, device=0):
+        self.fuser, self.device, self.ns = fuser, device, len(problems)
+        self.parts = [_sin_map_arrays(p["map"]) for p in problems]
+        prob, k0, m0 = [], 0, 0
+        for (kfs, M, _), p in zip(self.parts, problems):
+            prob.append([k0, len(kfs), m0, M, int(p["cur"])])
+            k0, m0 = k0 + len(kfs), m0 + M
+        self.prob = np.array(prob or [[0, 0, 0, 0, 0]], np.int32)
+        self.K, self.M = max(1, k0), max(1, m0)
+        self.pitch = P = max([1] + [k["n"] for kfs, _, _ in self.parts for k in kfs])
+        self.list_pitch = L = max([P] + [M for _, M, _ in self.parts])
+        K, M, S = self.K, self.M, max(1, self.ns)
+        h = self.host = dict(id=np.zeros(K, np.int32), n=np.zeros(K, np.int32), T=np.zeros((K, 16), np.float32),
+                             kps_un=np.zeros((K, P), KP_DTYPE), uright=np.full((K, P), -1, np.float32),
+                             kdesc=np.zeros((K, P, 32), np.uint8), mp=np.full((K, P), -1, np.int32),
+                             ordered=np.full((K, LM_MAX_MAP_KF), -1, np.int32))
+        for name, dt, w in _SIN_POINT_IO:
+            h[name] = np.zeros((M, w) if w > 1 else (M,), dt)
+        h["bad"][:] = 1
+        for (kfs, Mp, pts), row in zip(self.parts, prob):
+            for j, k in enumerate(kfs):
+                g, n = row[0] + j, k["n"]
+                h["id"][g], h["n"][g], h["T"][g], h["ordered"][g] = k["id"], n, k["Tcw"], k["ordered"]
+                h["kps_un"][g, :n], h["uright"][g, :n] = k["kps_un"], k["uright"]
+                h["kdesc"][g, :n], h["mp"][g, :n] = k["desc"], k["mp"]
+            for name, _, _ in _SIN_POINT_IO:
+                h[name][row[2]:row[2] + Mp] = pts[name]
+        mk = lambda a: DeviceBuffer.from_array(a, device)
+        b = self.bufs = {k: mk(v) for k, v in h.items()}
+        b.update(prob=mk(self.prob), replaced_by=DeviceBuffer(M * 4, device), n_obs=DeviceBuffer(M * 4, device),
+                 obs=DeviceBuffer(M * LM_MAX_MAP_KF * 2, device), desc_src=DeviceBuffer(M * 8, device),
+                 mark=DeviceBuffer(M, device), result=DeviceBuffer(S * C.sizeof(LmSinResult), device),
+                 list=DeviceBuffer(S * L * 4, device), search=DeviceBuffer(S * L * 4, device),
+                 err=mk(np.zeros(1, np.int32)))
+        self.batch = LmSinDeviceBatch(
+            K, P, M, L, *[b[k].ptr for k in (
+                "prob", "id", "n", "T", "kps_un", "uright", "kdesc", "mp", "ordered", "xyz", "normal",
+                "min_dist", "max_dist", "desc", "ref_kf", "bad", "n_visible", "n_found", "replaced_by",
+                "n_obs", "obs", "desc_src", "mark", "result", "list", "search", "err")])
+
+    def upload(self):
+        for name in ("mp",) + tuple(n for n, _, _ in _SIN_POINT_IO):
+            a = self.host[name]
+            check(lib().orbpl_memcpy_htod(self.device, self.bufs[name].ptr, _ptr(a), a.nbytes),
+                  "orbpl_memcpy_htod")
+
+    def run(self, stream=None):
+        check(lib().orblm_search_in_neighbors_batch_device(
+            *self.fuser._consts(), C.byref(self.batch), self.ns, stream),
+            "orblm_search_in_neighbors_batch_device")
+
+    def run_phases(self, stream=None):
+        """run() with in-kernel time stamps: per problem the microseconds spent in
+        the Fuse calls' search phases, in their commit phases, and in the whole
+        workgroup (synchronises)"""
+        ticks = DeviceBuffer(max(1, self.ns) * 24, self.device)
+        check(lib().orblm_debug_search_in_neighbors_phases(
+            *self.fuser._consts(), C.byref(self.batch), self.ns, stream, ticks.ptr),
+            "orblm_debug_search_in_neighbors_phases")
+        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
+        return ticks.download(np.int64, (max(1, self.ns), 3))[:self.ns] / 100.0
+
+    def download(self):
+        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
+        b, K, M, P = self.bufs, self.K, self.M, self.pitch
+        if int(b["err"].download(np.int32, 1)[0]):
+            raise OrbplError("orblm_search_in_neighbors_batch_device: candidate list overflow")
+        mp = b["mp"].download(np.int32, (K, P))
+        pool = {name: b[name].download(dt, (M, w) if w > 1 else (M,))
+                for name, dt, w in _SIN_POINT_IO + _SIN_POINT_OUT}
+        res = np.frombuffer(b["result"].download(np.uint8, max(1, self.ns) * C.sizeof(LmSinResult)).tobytes(),
+                            np.uint8)
+        outs = []
+        for s, ((kfs, Mp, _), row) in enumerate(zip(self.parts, self.prob)):
+            out = {name: pool[name][row[2]:row[2] + Mp].copy() for name in pool}
+            out["mp"] = [mp[row[0] + j, :k["n"]].copy() for j, k in enumerate(kfs)]
+            r = LmSinResult.from_buffer_copy(res[s * C.sizeof(LmSinResult):(s + 1) * C.sizeof(LmSinResult)].tobytes())
+            outs.append(_sin_result_out(out, r))
+        return outs
