@@ -327,7 +327,8 @@ int orbv_transform(orbv_vocab* v, int device, const uint8_t* desc, int n, int le
 /* The same for nframes device-resident frames: frame f's descriptors at
  * d_desc + f * desc_pitch * 32 (d_n[f] of them, <= max_n <= 4096); outputs
  * per frame at f * out_pitch (feature word / weight / node, BowVector), the
- * BowVector length in d_bow_n[f]; d_err bit 1 = a frame above 4096 features.
+ * BowVector length in d_bow_n[f]; a frame with d_n[f] > max_n is cut to its
+ * first max_n features and sets *d_err |= 2. At most 2^20 - 1 words.
  * `stream` = a hipStream_t (NULL: the vocabulary's own stream). */
 int orbv_transform_batch_device(orbv_vocab* v, const uint8_t* d_desc, int64_t desc_pitch,
                                 const int* d_n, int nframes, int max_n, int levelsup,

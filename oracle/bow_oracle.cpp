@@ -216,7 +216,7 @@ int oracle_voc_transform(void* h, const uint8_t* desc, int n, int levelsup, uint
   const Voc* v = static_cast<const Voc*>(h);
   std::map<uint32_t, double> bv;   // BowVector : std::map<WordId, WordValue>
   *bow_n = 0;
-  if (v->nodes.size() <= 1 || v->nodes[0].children.empty()) {
+  if (v->nwords == 0) {   // empty(): m_words.empty()
     for (int i = 0; i < n; i++) feat_node[i] = -1;
     return 0;
   }

@@ -62,8 +62,9 @@ struct BowBatch {
   double* bow_vals;
   int* bow_n;
   long long out_pitch;
-  int* err;                     // bit 1: more than kBowMaxFeat (or cap) features
+  int* err;                     // value 2: a frame with more than max_n features (clamped)
   int cap;                      // k_bow_vector's LDS keys: a power of two >= max_n
+  int max_n;                    // features per frame k_bow_words was launched for
 };
 
 }  // namespace
@@ -83,7 +84,7 @@ constexpr int kBowBatch = 10;   // the k of ORBvoc (and the bench vocabulary)
 
 __global__ void __launch_bounds__(256) k_bow_words(VocDev v, BowBatch b) {
   const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  const int n = b.n[f];
+  const int n = min(b.n[f], b.max_n);
   if (i >= n) return;
   const uint4* d = reinterpret_cast<const uint4*>(b.desc + ((long long)f * b.desc_pitch + i) * 32);
   const uint4 a0 = d[0], a1 = d[1];
@@ -140,9 +141,9 @@ __global__ void __launch_bounds__(256) k_bow_vector(VocDev v, BowBatch b) {
   __shared__ double s_norm;
   const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   int n = b.n[f];
-  if (n > b.cap) {
+  if (n > b.max_n) {   // the slots past max_n were not written by k_bow_words
     if (t == 0) atomicOr(b.err, 2);
-    n = b.cap;
+    n = b.max_n;
   }
   const long long o = (long long)f * b.out_pitch;
   int np = 1;
@@ -297,7 +298,9 @@ int build_csr(orbv_vocab* v) {
   v->n_words = 0;
   for (int i = 0; i < nn; i++)
     if (v->leaf_flag[i]) v->word[i] = v->n_words++;
-  if (v->n_words > (1 << 20)) return arg_fail("vocabulary: more than 2^20 words");
+  // sort keys word << 12 | feature: the last word's key with feature 4095
+  // must stay below kNoKey
+  if (v->n_words >= (1 << 20)) return arg_fail("vocabulary: more than 2^20 - 1 words");
   if (nn >= (1 << 21) - 1) return arg_fail("vocabulary: more than 2^21 - 2 nodes");
   return ORBPL_OK;
 }
@@ -507,7 +510,7 @@ int orbv_transform_batch_device(orbv_vocab* v, const uint8_t* d_desc, int64_t de
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   VocDev vd{c->d_child_start, c->d_child, reinterpret_cast<const uint4*>(c->d_desc), c->d_word,
             c->d_weight, v->L, norm_of(v->scoring), (v->weighting == 0 || v->weighting == 1) ? 1 : 0};
-  if (v->parent.size() <= 1) {   // empty(): nothing is added
+  if (v->n_words == 0) {   // empty() (m_words.empty()): nothing is added
     HIP_CHECK(hipMemsetAsync(d_bow_n, 0, 4 * (size_t)nframes, s));
     HIP_CHECK(hipMemsetAsync(d_feat_node, 0xFF, 4 * (size_t)(out_pitch * nframes), s));
     return ORBPL_OK;
@@ -515,7 +518,7 @@ int orbv_transform_batch_device(orbv_vocab* v, const uint8_t* d_desc, int64_t de
   int cap = 1;
   while (cap < max_n) cap <<= 1;
   BowBatch b{d_desc, desc_pitch, d_n, levelsup, d_feat_node, d_feat_word, d_feat_weight,
-             d_bow_words, d_bow_vals, d_bow_n, out_pitch, d_err, cap};
+             d_bow_words, d_bow_vals, d_bow_n, out_pitch, d_err, cap, max_n};
   if (max_n > 0)
     hipLaunchKernelGGL(k_bow_words, dim3((max_n + 255) / 256, nframes), dim3(256), 0, s, vd, b);
   set_smem_attr((const void*)k_bow_vector, (size_t)kBowMaxFeat * 12);
