@@ -1017,6 +1017,159 @@ int orbm_fuse(const orbpl_camera* cam, const float* scale_factors, const float* 
               int* n_fused, int32_t* best_idx, int32_t* best_dist, int32_t* reason);
 
 /* ------------------------------------------------------------------------
+ * LocalMapping::KeyFrameCulling() (LocalMapping.cc:1224-1319), non-monocular,
+ * with KeyFrame::SetBadFlag / EraseConnection / UpdateBestCovisibles
+ * (KeyFrame.cc:526-650) and MapPoint::EraseObservation / SetBadFlag
+ * (MapPoint.cc:111-168), for many independent maps in one launch (DESIGN.md
+ * P48-P51). The call mutates the map and the covisibility graph it is given.
+ * Not called by orbpl_tracker_step (P23 stays). Map lines are not touched:
+ * the fork's KeyFrame::SetBadFlag leaves mvpMapLines alone, so lines keep
+ * observing a culled keyframe. After a call a map may hold bad keyframes:
+ * orblm_search_in_neighbors assumes none is (P41), so a caller who chains the
+ * two must take the culled keyframes out of the table it passes there.
+ * ---------------------------------------------------------------------- */
+#define ORBLM_MAX_CULL_LIST 63     /* the current keyframe's covisibles: every other keyframe */
+#define ORBLM_KFC_KEPT 0           /* nRedundantObservations <= 0.9 * nMPs              */
+#define ORBLM_KFC_CULLED 1         /* SetBadFlag ran to its end                         */
+#define ORBLM_KFC_FIRST 2          /* mnId == 0: skipped before the count               */
+#define ORBLM_KFC_DEFERRED 3       /* redundant, but mbNotErase: mbToBeErased set only  */
+/* vpLocalKeyFrames as copied at entry (table indices) and, per list entry,
+ * nMPs, nRedundantObservations and what became of it; n_points_bad = the
+ * number of map points the call set bad. */
+typedef struct orblm_kfc_result {
+  int32_t list[ORBLM_MAX_CULL_LIST];
+  int32_t n_list;
+  int32_t n_mps[ORBLM_MAX_CULL_LIST];
+  int32_t n_redundant[ORBLM_MAX_CULL_LIST];
+  int32_t action[ORBLM_MAX_CULL_LIST];
+  int32_t n_points_bad;
+} orblm_kfc_result;
+/* A map, its current keyframe and the graph state orblm_map lacks, per map of
+ * nkf keyframes: depth[k] = mvDepth of keyframe k (map.kf[k].n floats; in);
+ * conn_w[nkf * nkf], row k = keyframe k's mConnectedKeyFrameWeights (0 = not
+ * connected; need not be symmetric; in/out); ordered[nkf * 64] = every
+ * keyframe's mvpOrderedConnectedKeyFrames as table indices, ended by -1 or
+ * the 64th entry (state of its own, not derived from conn_w; in/out;
+ * map.kf[k].ordered is not read); parent[nkf] = mpParent (-1 none; in/out);
+ * not_erase[nkf] = mbNotErase (in); kf_bad[nkf] = mbBad (in/out);
+ * to_be_erased[nkf] = mbToBeErased (out: 1 where the call deferred a cull);
+ * the observations are derived from the slot arrays at entry, those of a
+ * keyframe that is bad at entry left out (SetBadFlag does not clear a culled
+ * keyframe's own slots, but its points no longer observe it);
+ * Tcp[16 * nkf] = mTcp, written only for a keyframe the call culled. Of the
+ * map the call writes the slot arrays, ref_kf, bad, n_obs and obs. */
+typedef struct orblm_kfc_problem {
+  orblm_map map;
+  int32_t cur;
+  const float* const* depth;
+  int32_t* conn_w;
+  int32_t* ordered;
+  int32_t* parent;
+  const uint8_t* not_erase;
+  uint8_t* kf_bad;
+  uint8_t* to_be_erased;
+  float* Tcp;
+  orblm_kfc_result result;  /* out */
+} orblm_kfc_problem;
+/* n problems, host pointers, one launch; th_depth is cam->th_depth.
+ * ORBPL_ERR_ARG before any device call: everything orblm_search_in_neighbors
+ * refuses for the map itself, and NULL graph arrays, a negative weight, a
+ * non-zero diagonal of conn_w, an ordered or parent entry outside the table or
+ * naming its own keyframe, an ordered list that names a keyframe twice, a
+ * keyframe with id != 0 and parent == -1 that is not bad, and an array that
+ * two problems share. */
+int orblm_keyframe_culling(const orbpl_camera* cam, int nlevels, orblm_kfc_problem* problems, int n);
+/* The same over pools in device memory, with the conventions of
+ * orblm_sin_device_batch: d_prob[5 * p ..] = (kf0, nkf, mp0, nmp, cur), every
+ * index relative to the problem's own range, ranges of two problems disjoint.
+ * Per keyframe g: d_kf_id, d_kf_n, d_kf_Tcw[16 g], d_kps_un / d_uright /
+ * d_depth / d_mp at g * kp_pitch, d_conn_w[64 g + j] = its weight towards
+ * keyframe j of its own map, d_ordered[64 g ..], d_parent, d_not_erase,
+ * d_kf_bad, d_to_be_erased (zeroed by the call), d_Tcp[16 g]. Per point m:
+ * d_ref_kf, d_bad (in/out), d_n_obs, d_obs[64 m] (out). Per problem:
+ * d_result[p]. A problem whose range lies outside the pools is not run and
+ * sets *d_err, which the caller zeroes beforehand. Asynchronous on `stream`,
+ * no readback; counts above a pitch are clamped on the device. */
+typedef struct orblm_kfc_device_batch {
+  int32_t nkf, kp_pitch, nmp;
+  const int32_t* d_prob;
+  const int32_t* d_kf_id;
+  const int32_t* d_kf_n;
+  const float* d_kf_Tcw;
+  const orbpl_keypoint* d_kps_un;
+  const float* d_uright;
+  const float* d_depth;
+  int32_t* d_mp;
+  int32_t* d_conn_w;
+  int32_t* d_ordered;
+  int32_t* d_parent;
+  const uint8_t* d_not_erase;
+  uint8_t* d_kf_bad;
+  uint8_t* d_to_be_erased;
+  float* d_Tcp;
+  int32_t* d_ref_kf;
+  uint8_t* d_bad;
+  int32_t* d_n_obs;
+  int16_t* d_obs;
+  orblm_kfc_result* d_result;
+  int32_t* d_err;
+} orblm_kfc_device_batch;
+int orblm_keyframe_culling_batch_device(const orbpl_camera* cam, const orblm_kfc_device_batch* b,
+                                        int n, void* stream);
+
+/* ------------------------------------------------------------------------
+ * LocalMapping::MapPointCulling() then MapLineCulling() (LocalMapping.cc:
+ * 246-340), non-monocular (nThObs = 3), on the recently added points and
+ * lines of many independent maps in one launch. Host entry
+ * only. Per list entry, in the reference's order: already bad (dropped from
+ * the list), GetFoundRatio() < 0.25f (SetBadFlag, dropped), age >= 2 and
+ * Observations() <= 3 (SetBadFlag, dropped), age >= 3 (dropped), else it
+ * stays. SetBadFlag: bad = 1, the slot in every observer goes to -1, n_obs is
+ * kept.
+ * ---------------------------------------------------------------------- */
+#define ORBLM_MAX_MAP_LINES (ORBLM_MAX_MAP_KF * ORBLM_MAX_LINES)
+#define ORBLM_RC_WAS_BAD 0
+#define ORBLM_RC_FOUND_RATIO 1
+#define ORBLM_RC_FEW_OBSERVATIONS 2
+#define ORBLM_RC_AGED_OUT 3
+#define ORBLM_RC_STAYS 4
+/* map: as above (the call writes the slot arrays, bad, n_obs, obs); kf_bad[nkf]
+ * = mbBad per keyframe (NULL: none is; a bad keyframe's slots give no
+ * observations, as in orblm_keyframe_culling); cur_id =
+ * mpCurrentKeyFrame->mnId; first_kf[M] = mnFirstKFid; recent[n_recent] =
+ * mlpRecentAddedMapPoints as point indices (in/out: what remains, in order;
+ * no entry may repeat) with reason[] per entry as passed in (out). Lines: L <=
+ * 64 * 256 of them; nl[k] <= 256 line features of keyframe k with their slot
+ * array ml[k] (-1 none; in/out); line_bad (in/out), line_n_visible,
+ * line_n_found, line_first_kf (may be -1), line_n_obs (the caller's nObs, not
+ * derived; in); recent_lines / n_recent_lines / line_reason the same way. */
+typedef struct orblm_recent_problem {
+  orblm_map map;
+  const uint8_t* kf_bad;
+  int32_t cur_id;
+  const int32_t* first_kf;
+  int32_t* recent;
+  int32_t n_recent;      /* in/out */
+  int32_t* reason;
+  int32_t L;
+  const int32_t* nl;
+  int32_t* const* ml;
+  uint8_t* line_bad;
+  const int32_t* line_n_visible;
+  const int32_t* line_n_found;
+  const int32_t* line_first_kf;
+  const int32_t* line_n_obs;
+  int32_t* recent_lines;
+  int32_t n_recent_lines;  /* in/out */
+  int32_t* line_reason;
+} orblm_recent_problem;
+/* ORBPL_ERR_ARG before any device call: what orblm_search_in_neighbors refuses
+ * for the map, NULL arrays, list entries outside the tables, a list entry that
+ * repeats, L outside [0, 64 * 256], nl outside [0, 256], a line slot outside
+ * [-1, L), and an array that two problems share. */
+int orblm_cull_recent(int nlevels, orblm_recent_problem* problems, int n);
+
+/* ------------------------------------------------------------------------
  * Optimizer::PoseOptimization / PoseOptimizationWithLines
  * (Optimizer.cc:375-619, 2132-2486): 4 rounds x 10 Levenberg-Marquardt
  * iterations on one SE3 vertex, Huber kernel in rounds 0-2, chi2 outlier

@@ -2478,3 +2478,255 @@ class SinDeviceProblems:
             r = LmSinResult.from_buffer_copy(res[s * C.sizeof(LmSinResult):(s + 1) * C.sizeof(LmSinResult)].tobytes())
             outs.append(_sin_result_out(out, r))
         return outs
+
+
+# ---------------------------------------------------------------------------
+# LocalMapping::KeyFrameCulling and MapPointCulling / MapLineCulling as batched
+# calls
+# ---------------------------------------------------------------------------
+LM_MAX_CULL_LIST, LM_MAX_LINES = 63, 256
+KFC_ACTIONS = ("kept", "culled", "first", "deferred")
+RECENT_REASONS = ("was_bad", "found_ratio", "few_observations", "aged_out", "stays")
+
+
+class LmKfcResult(C.Structure):
+    """orblm_kfc_result"""
+    _fields_ = [("list", C.c_int32 * LM_MAX_CULL_LIST), ("n_list", C.c_int32),
+                ("n_mps", C.c_int32 * LM_MAX_CULL_LIST), ("n_redundant", C.c_int32 * LM_MAX_CULL_LIST),
+                ("action", C.c_int32 * LM_MAX_CULL_LIST), ("n_points_bad", C.c_int32)]
+
+
+class LmKfcProblem(C.Structure):
+    """orblm_kfc_problem"""
+    _fields_ = ([("map", LmMap), ("cur", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("depth", "conn_w", "ordered", "parent", "not_erase", "kf_bad",
+                                           "to_be_erased", "Tcp")] + [("result", LmKfcResult)])
+
+
+class LmKfcDeviceBatch(C.Structure):
+    """orblm_kfc_device_batch: pools of keyframes, map points and the graph (see include/orbpl.h)"""
+    _fields_ = ([(k, C.c_int32) for k in ("nkf", "kp_pitch", "nmp")] +
+                [(k, C.c_void_p) for k in (
+                    "d_prob", "d_kf_id", "d_kf_n", "d_kf_Tcw", "d_kps_un", "d_uright", "d_depth", "d_mp",
+                    "d_conn_w", "d_ordered", "d_parent", "d_not_erase", "d_kf_bad", "d_to_be_erased",
+                    "d_Tcp", "d_ref_kf", "d_bad", "d_n_obs", "d_obs", "d_result", "d_err")])
+
+
+class LmRecentProblem(C.Structure):
+    """orblm_recent_problem"""
+    _fields_ = [("map", LmMap), ("kf_bad", C.c_void_p), ("cur_id", C.c_int32), ("first_kf", C.c_void_p),
+                ("recent", C.c_void_p), ("n_recent", C.c_int32), ("reason", C.c_void_p), ("L", C.c_int32),
+                ("nl", C.c_void_p), ("ml", C.c_void_p), ("line_bad", C.c_void_p),
+                ("line_n_visible", C.c_void_p), ("line_n_found", C.c_void_p),
+                ("line_first_kf", C.c_void_p), ("line_n_obs", C.c_void_p), ("recent_lines", C.c_void_p),
+                ("n_recent_lines", C.c_int32), ("line_reason", C.c_void_p)]
+
+
+def _declare_cull(L):
+    vp, i = C.c_void_p, C.c_int
+    L.orblm_keyframe_culling.argtypes = [vp, i, vp, i]
+    L.orblm_keyframe_culling_batch_device.argtypes = [vp, vp, i, vp]
+    L.orblm_cull_recent.argtypes = [i, vp, i]
+
+
+_declare_before_cull = _declare
+
+
+def _declare(L):  # noqa: F811
+    _declare_before_cull(L)
+    _declare_cull(L)
+
+
+def _kfc_graph_arrays(prob, kfs):
+    """copies of a culling problem's graph state (the call writes them)"""
+    K = len(kfs)
+    ordered = np.full((K, LM_MAX_MAP_KF), -1, np.int32)
+    for k, o in enumerate(prob["ordered"]):
+        o = [int(x) for x in o][:LM_MAX_MAP_KF]
+        ordered[k, :len(o)] = o
+    depth = [_c(d, np.float32).reshape(-1).copy() for d in prob["depth"]]
+    assert len(depth) == K and all(len(d) == k["n"] for d, k in zip(depth, kfs))
+    Tcp = np.array(prob["Tcp"], np.float32).reshape(K, 16) if "Tcp" in prob else np.zeros((K, 16), np.float32)
+    return dict(depth=depth, conn_w=np.array(prob["conn_w"], np.int32).reshape(K, K), ordered=ordered,
+                parent=np.array(prob["parent"], np.int32).reshape(K),
+                not_erase=np.array(prob["not_erase"], np.uint8).reshape(K),
+                kf_bad=np.array(prob["kf_bad"], np.uint8).reshape(K),
+                to_be_erased=np.zeros(K, np.uint8), Tcp=Tcp)
+
+
+def _kfc_result_out(out, g, r):
+    n = r.n_list
+    out.update({k: g[k] for k in ("conn_w", "ordered", "parent", "kf_bad", "to_be_erased", "Tcp")})
+    out.update(list=np.array(r.list[:n], np.int32), n_mps=np.array(r.n_mps[:n], np.int32),
+               n_redundant=np.array(r.n_redundant[:n], np.int32), action=np.array(r.action[:n], np.int32),
+               n_points_bad=int(r.n_points_bad))
+    return out
+
+
+class MapCuller:
+    """LocalMapping::KeyFrameCulling and MapPointCulling / MapLineCulling
+    (non-monocular) for many independent maps in one launch each. A map is the
+    dict NeighborFuser takes (a keyframe's `ordered` is not read here).
+
+    keyframes(problems): a problem is dict(map, cur, depth=[mvDepth per keyframe],
+    conn_w=(nkf, nkf) weights, ordered=[list per keyframe], parent, not_erase,
+    kf_bad[, Tcp]). A result holds the updated map arrays (as NeighborFuser's),
+    conn_w, ordered (nkf, 64; -1 ends a list), parent, kf_bad, to_be_erased, Tcp
+    and list, n_mps, n_redundant, action (KFC_ACTIONS), n_points_bad.
+
+    recent(problems): a problem is dict(map, cur_id, first_kf, recent[, kf_bad],
+    lines=dict(ml=[slot array per keyframe], bad, n_visible, n_found, first_kf,
+    n_obs), recent_lines). A result holds the updated map arrays, recent, reason
+    (RECENT_REASONS, per entry as passed in), ml, line_bad, recent_lines,
+    line_reason. The inputs are not modified."""
+
+    def __init__(self, camera, scale_factors, level_sigma2):
+        self.camera = camera
+        self.scale = _c(scale_factors, np.float32)
+        self.sigma2 = _c(level_sigma2, np.float32)
+        assert len(self.scale) == len(self.sigma2)
+
+    def keyframes(self, problems):
+        keep, P, parts = [], (LmKfcProblem * max(1, len(problems)))(), []
+        for p, prob in enumerate(problems):
+            P[p].map, kfs, pts = _sin_map_struct(prob["map"], keep)
+            P[p].cur = int(prob["cur"])
+            g = _kfc_graph_arrays(prob, kfs)
+            dptr = (C.c_void_p * max(1, len(kfs)))(*[_ptr(d) for d in g["depth"]])
+            keep += [g, dptr]
+            P[p].depth = C.cast(dptr, C.c_void_p)
+            for name in ("conn_w", "ordered", "parent", "not_erase", "kf_bad", "to_be_erased", "Tcp"):
+                setattr(P[p], name, _ptr(g[name]))
+            parts.append((kfs, pts, g))
+        check(lib().orblm_keyframe_culling(C.byref(self.camera), len(self.scale), P, len(problems)),
+              "orblm_keyframe_culling")
+        return [_kfc_result_out(_sin_map_out(kfs, pts), g, P[p].result)
+                for p, (kfs, pts, g) in enumerate(parts)]
+
+    def keyframes_device(self, pools, stream=None):
+        """orblm_keyframe_culling_batch_device over a KfcDeviceProblems: no host round trip"""
+        check(lib().orblm_keyframe_culling_batch_device(
+            C.byref(self.camera), C.byref(pools.batch), pools.ns, stream),
+            "orblm_keyframe_culling_batch_device")
+
+    def recent(self, problems):
+        keep, P, parts = [], (LmRecentProblem * max(1, len(problems)))(), []
+        i32 = lambda a: np.array(a, np.int32).reshape(-1)
+        for p, prob in enumerate(problems):
+            q = P[p]
+            q.map, kfs, pts = _sin_map_struct(prob["map"], keep)
+            K = len(kfs)
+            ln = prob["lines"]
+            a = dict(first_kf=i32(prob["first_kf"]), recent=i32(prob["recent"]),
+                     recent_lines=i32(prob["recent_lines"]), line_bad=np.array(ln["bad"], np.uint8).reshape(-1),
+                     line_n_visible=i32(ln["n_visible"]), line_n_found=i32(ln["n_found"]),
+                     line_first_kf=i32(ln["first_kf"]), line_n_obs=i32(ln["n_obs"]),
+                     ml=[i32(x) for x in ln["ml"]])
+            assert len(a["ml"]) == K
+            a["nl"] = np.array([len(x) for x in a["ml"]], np.int32)
+            a["reason"] = np.zeros(len(a["recent"]), np.int32)
+            a["line_reason"] = np.zeros(len(a["recent_lines"]), np.int32)
+            mlptr = (C.c_void_p * max(1, K))(*[_ptr(x) for x in a["ml"]])
+            keep += [a, mlptr]
+            if "kf_bad" in prob:
+                a["kf_bad"] = np.array(prob["kf_bad"], np.uint8).reshape(K)
+                q.kf_bad = _ptr(a["kf_bad"])
+            q.cur_id, q.L = int(prob["cur_id"]), len(a["line_bad"])
+            q.n_recent, q.n_recent_lines = len(a["recent"]), len(a["recent_lines"])
+            q.ml = C.cast(mlptr, C.c_void_p)
+            for name in ("first_kf", "recent", "reason", "nl", "line_bad", "line_n_visible", "line_n_found",
+                         "line_first_kf", "line_n_obs", "recent_lines", "line_reason"):
+                setattr(q, name, _ptr(a[name]))
+            parts.append((kfs, pts, a))
+        check(lib().orblm_cull_recent(len(self.scale), P, len(problems)), "orblm_cull_recent")
+        outs = []
+        for p, (kfs, pts, a) in enumerate(parts):
+            out = _sin_map_out(kfs, pts)
+            out.update(recent=a["recent"][:P[p].n_recent].copy(), reason=a["reason"], ml=a["ml"],
+                       line_bad=a["line_bad"], recent_lines=a["recent_lines"][:P[p].n_recent_lines].copy(),
+                       line_reason=a["line_reason"])
+            outs.append(out)
+        return outs
+
+
+class KfcDeviceProblems:
+    """The device pools of orblm_keyframe_culling_batch_device for a list of
+    problems (as MapCuller.keyframes takes them): SinDeviceProblems' layout for the
+    keyframes and points, plus depth at kp_pitch and the graph arrays (conn_w
+    rows at a pitch of 64). MapCuller.keyframes_device(pools) launches without a
+    host round trip, download() synchronises and returns the same per-problem
+    results. A run mutates the pools: upload() restores the inputs."""
+
+    _IO = ("mp", "conn_w", "ordered", "parent", "kf_bad", "Tcp", "ref_kf", "bad")
+
+    def __init__(self, culler, problems, device=0):
+        self.culler, self.device, self.ns = culler, device, len(problems)
+        self.parts = [_sin_map_arrays(p["map"]) for p in problems]
+        self.graphs = [_kfc_graph_arrays(p, kfs) for p, (kfs, _, _) in zip(problems, self.parts)]
+        prob, k0, m0 = [], 0, 0
+        for (kfs, M, _), p in zip(self.parts, problems):
+            prob.append([k0, len(kfs), m0, M, int(p["cur"])])
+            k0, m0 = k0 + len(kfs), m0 + M
+        self.prob = np.array(prob or [[0, 0, 0, 0, 0]], np.int32)
+        self.K, self.M = max(1, k0), max(1, m0)
+        self.pitch = P = max([1] + [k["n"] for kfs, _, _ in self.parts for k in kfs])
+        K, M, S, W = self.K, self.M, max(1, self.ns), LM_MAX_MAP_KF
+        h = self.host = dict(
+            id=np.zeros(K, np.int32), n=np.zeros(K, np.int32), T=np.zeros((K, 16), np.float32),
+            kps_un=np.zeros((K, P), KP_DTYPE), uright=np.full((K, P), -1, np.float32),
+            depth=np.full((K, P), -1, np.float32), mp=np.full((K, P), -1, np.int32),
+            conn_w=np.zeros((K, W), np.int32), ordered=np.full((K, W), -1, np.int32),
+            parent=np.full(K, -1, np.int32), not_erase=np.zeros(K, np.uint8), kf_bad=np.zeros(K, np.uint8),
+            Tcp=np.zeros((K, 16), np.float32), ref_kf=np.zeros(M, np.int32), bad=np.ones(M, np.uint8))
+        for (kfs, Mp, pts), g, row in zip(self.parts, self.graphs, prob):
+            for j, k in enumerate(kfs):
+                x, n = row[0] + j, k["n"]
+                h["id"][x], h["n"][x], h["T"][x] = k["id"], n, k["Tcw"]
+                h["kps_un"][x, :n], h["uright"][x, :n], h["mp"][x, :n] = k["kps_un"], k["uright"], k["mp"]
+                h["depth"][x, :n] = g["depth"][j]
+                h["conn_w"][x, :len(kfs)] = g["conn_w"][j]
+                for name in ("ordered", "parent", "not_erase", "kf_bad", "Tcp"):
+                    h[name][x] = g[name][j]
+            h["ref_kf"][row[2]:row[2] + Mp], h["bad"][row[2]:row[2] + Mp] = pts["ref_kf"], pts["bad"]
+        mk = lambda a: DeviceBuffer.from_array(a, device)
+        b = self.bufs = {k: mk(v) for k, v in h.items()}
+        b.update(prob=mk(self.prob), to_be_erased=DeviceBuffer(K, device), n_obs=DeviceBuffer(M * 4, device),
+                 obs=DeviceBuffer(M * W * 2, device), result=DeviceBuffer(S * C.sizeof(LmKfcResult), device),
+                 err=mk(np.zeros(1, np.int32)))
+        self.batch = LmKfcDeviceBatch(
+            K, P, M, *[b[k].ptr for k in (
+                "prob", "id", "n", "T", "kps_un", "uright", "depth", "mp", "conn_w", "ordered", "parent",
+                "not_erase", "kf_bad", "to_be_erased", "Tcp", "ref_kf", "bad", "n_obs", "obs", "result",
+                "err")])
+
+    def upload(self):
+        for name in self._IO:
+            a = self.host[name]
+            check(lib().orbpl_memcpy_htod(self.device, self.bufs[name].ptr, _ptr(a), a.nbytes),
+                  "orbpl_memcpy_htod")
+
+    def run(self, stream=None):
+        self.culler.keyframes_device(self, stream)
+
+    def download(self):
+        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
+        b, K, M, P, W = self.bufs, self.K, self.M, self.pitch, LM_MAX_MAP_KF
+        if int(b["err"].download(np.int32, 1)[0]):
+            raise OrbplError("orblm_keyframe_culling_batch_device: a problem lies outside the pools")
+        mp = b["mp"].download(np.int32, (K, P))
+        kf = dict(conn_w=b["conn_w"].download(np.int32, (K, W)), ordered=b["ordered"].download(np.int32, (K, W)),
+                  parent=b["parent"].download(np.int32, K), kf_bad=b["kf_bad"].download(np.uint8, K),
+                  to_be_erased=b["to_be_erased"].download(np.uint8, K), Tcp=b["Tcp"].download(np.float32, (K, 16)))
+        pt = dict(ref_kf=b["ref_kf"].download(np.int32, M), bad=b["bad"].download(np.uint8, M),
+                  n_obs=b["n_obs"].download(np.int32, M), obs=b["obs"].download(np.int16, (M, W)))
+        sz = C.sizeof(LmKfcResult)
+        res = b["result"].download(np.uint8, max(1, self.ns) * sz).tobytes()
+        outs = []
+        for s, ((kfs, Mp, pts), row) in enumerate(zip(self.parts, self.prob)):
+            out = {name: v.copy() for name, v in pts.items()}
+            out.update({name: v[row[2]:row[2] + Mp].copy() for name, v in pt.items()})
+            out["mp"] = [mp[row[0] + j, :k["n"]].copy() for j, k in enumerate(kfs)]
+            g = {name: v[row[0]:row[0] + len(kfs)].copy() for name, v in kf.items()}
+            g["conn_w"] = g["conn_w"][:, :len(kfs)].copy()
+            outs.append(_kfc_result_out(out, g, LmKfcResult.from_buffer_copy(res[s * sz:(s + 1) * sz])))
+        return outs

@@ -46,6 +46,7 @@
 #include "block_ops.h"
 #include "host_stage.h"
 #include "lsd_math.h"
+#include "map_rows.h"
 #include "match_common.h"
 #include "orbpl_runtime.h"
 #include "track_kernels.h"
@@ -56,7 +57,6 @@ namespace {
 constexpr int kSnThreads = 256;
 constexpr int kSnKF = ORBLM_MAX_MAP_KF;
 constexpr int kSnMaxKp = ORBLM_MAX_KEYPOINTS;
-constexpr int kSnMaxPoints = ORBLM_MAX_MAP_KF * ORBLM_MAX_KEYPOINTS;
 constexpr int kSnThLow = 50;          // ORBmatcher::TH_LOW
 constexpr int kSearchPass = 15;       // the search found bestDist <= TH_LOW
 
@@ -93,11 +93,6 @@ struct SnShared {
   long long ticks[2];
 };
 
-// what a problem owns of the pools
-struct SnView {
-  int kf0, nkf, mp0, nmp, cur;
-};
-
 __device__ __forceinline__ int pack_search(int reason, int dist, int idx) {
   return (reason << 24) | (dist << 12) | (idx & 0xfff);
 }
@@ -109,7 +104,7 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 __device__ __forceinline__ int kf_count(const orblm_sin_device_batch& b, const SnView& V, int k) {
-  return max(0, min(b.d_kf_n[V.kf0 + k], min(b.kp_pitch, kSnMaxKp)));
+  return kf_count(b.d_kf_n, b.kp_pitch, V, k);
 }
 
 // The observers of point m (global index gm) in keyframe-id order, one per
@@ -454,27 +449,19 @@ __global__ void __launch_bounds__(kSnThreads) k_search_in_neighbors(SnArgs a) {
   __shared__ SnShared S;
   const orblm_sin_device_batch& b = a.b;
   const int t = threadIdx.x, p = blockIdx.x, lane = t & 63, wave = t >> 6;
-  SnView V;
-  V.kf0 = b.d_prob[5 * p];
-  V.nkf = b.d_prob[5 * p + 1];
-  V.mp0 = b.d_prob[5 * p + 2];
-  V.nmp = b.d_prob[5 * p + 3];
-  V.cur = b.d_prob[5 * p + 4];
+  const SnView V = load_view(b.d_prob, p);
   orblm_sin_result* R = b.d_result + p;
   int32_t* Ri = reinterpret_cast<int32_t*>(R);
   for (int i = t; i < (int)(sizeof(orblm_sin_result) / 4); i += kSnThreads) Ri[i] = 0;
   // a range outside the pools, or no current keyframe: nothing to do
-  if (V.kf0 < 0 || V.nkf < 1 || V.nkf > kSnKF || V.kf0 + V.nkf > b.nkf || V.mp0 < 0 || V.nmp < 0 ||
-      V.nmp > kSnMaxPoints || V.mp0 + V.nmp > b.nmp)
-    return;
+  if (!view_in_pools(V, b.nkf, b.nmp)) return;
   const int kf = a.fuse_only ? a.fuse_kf : V.cur;
   if (kf < 0 || kf >= V.nkf) return;
   int32_t* list = b.d_list + (long long)p * b.list_pitch;
   int32_t* search = b.d_search + (long long)p * b.list_pitch;
   // ---- the map as the call sees it: observation rows from the slots ----
-  for (long long i = t; i < (long long)V.nmp * 8; i += kSnThreads)
-    reinterpret_cast<uint4*>(b.d_obs + (long long)V.mp0 * kSnKF)[i] =
-        make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+  const MapRows rows = {b.d_kf_n, b.d_uright, b.d_mp, b.d_n_obs, b.d_obs, b.kp_pitch, nullptr};
+  clear_observation_rows<kSnThreads>(rows, V);
   for (int m = t; m < V.nmp; m += kSnThreads) {
     const long long gm = (long long)V.mp0 + m;
     b.d_replaced_by[gm] = -1;
@@ -492,26 +479,8 @@ __global__ void __launch_bounds__(kSnThreads) k_search_in_neighbors(SnArgs a) {
     }
   }
   __syncthreads();
-  if (t < V.nkf) {
-    int rank = 0;
-    for (int j = 0; j < V.nkf; j++) rank += S.id[j] < S.id[t] || (S.id[j] == S.id[t] && j < t);
-    S.by_id[rank] = t;
-  }
-  for (int k = 0; k < V.nkf; k++) {
-    const long long kb = (long long)(V.kf0 + k) * b.kp_pitch;
-    const int nk = kf_count(b, V, k);
-    for (int i = t; i < nk; i += kSnThreads) {
-      const int m = b.d_mp[kb + i];
-      if (m < 0) continue;
-      if (m >= V.nmp) {
-        b.d_mp[kb + i] = -1;
-        continue;
-      }
-      const long long gm = (long long)V.mp0 + m;
-      b.d_obs[gm * kSnKF + k] = (int16_t)i;
-      atomicAdd(&b.d_n_obs[gm], b.d_uright[kb + i] >= 0.0f ? 2 : 1);
-    }
-  }
+  rank_by_id(S.id, V.nkf, S.by_id, nullptr);
+  derive_observation_rows<kSnThreads>(rows, V);
   __syncthreads();
   if (a.fuse_only) {
     const int n = max(0, min(a.fuse_n, b.list_pitch));
@@ -683,45 +652,6 @@ int check_sn_batch(const orblm_sin_device_batch* b) {
 using namespace orbpl;
 
 namespace {
-
-// the refusals of one map (before any device call); obs_of_ref: scratch
-int check_map(const orblm_map& m, int nlevels, std::vector<int32_t>& stamp,
-              std::vector<uint8_t>& ref_seen) {
-  if (m.nkf < 1 || m.nkf > kSnKF) return arg_fail("map with no keyframe or more than 64");
-  if (!m.kf) return arg_fail("NULL keyframe table");
-  if (m.M < 0 || m.M > kSnMaxPoints) return arg_fail("map points outside [0, 64 * 2048]");
-  if (m.M > 0 && (!m.xyz || !m.normal || !m.min_dist || !m.max_dist || !m.desc || !m.ref_kf ||
-                  !m.bad || !m.n_visible || !m.n_found || !m.replaced_by || !m.n_obs || !m.obs ||
-                  !m.desc_src))
-    return arg_fail("NULL map point arrays");
-  stamp.assign((size_t)m.M, -1);
-  ref_seen.assign((size_t)m.M, 0);
-  for (int k = 0; k < m.nkf; k++) {
-    const orblm_map_keyframe& f = m.kf[k];
-    if (!f.Tcw) return arg_fail("NULL keyframe pose");
-    if (f.n < 0 || f.n > kSnMaxKp) return arg_fail("keyframe with more than 2048 features");
-    if (f.n > 0 && (!f.kps_un || !f.uright || !f.desc || !f.mp)) return arg_fail("NULL keyframe arrays");
-    for (int j = 0; j < k; j++)
-      if (m.kf[j].id == f.id) return arg_fail("two keyframes of a map with one id");
-    for (int i = 0; i < f.n; i++) {
-      if (f.kps_un[i].octave < 0 || f.kps_un[i].octave >= nlevels)
-        return arg_fail("keypoint octave outside [0, nlevels)");
-      const int p = f.mp[i];
-      if (p < -1 || p >= m.M) return arg_fail("slot index outside [-1, M)");
-      if (p < 0) continue;
-      if (stamp[p] == k) return arg_fail("map point twice in one keyframe");
-      stamp[p] = k;
-      if (m.ref_kf[p] == k) ref_seen[p] = 1;
-    }
-    if (f.ordered)
-      for (int x = 0; x < kSnKF && f.ordered[x] >= 0; x++)
-        if (f.ordered[x] >= m.nkf || f.ordered[x] == k)
-          return arg_fail("ordered entry outside the table or naming its own keyframe");
-  }
-  for (int p = 0; p < m.M; p++)
-    if (!m.bad[p] && !ref_seen[p]) return arg_fail("good map point whose ref_kf does not observe it");
-  return ORBPL_OK;
-}
 
 // The pools of a host call: every map of the call, flattened.
 struct SnHostPool {
