@@ -552,6 +552,264 @@ typedef struct orbpnp_device_batch {
 int orbpnp_iterate_batch_device(const orbpnp_device_batch* b, int nsolvers, int n_iterations,
                                 void* stream);
 
+/* Sim3Solver (Sim3Solver.cc): Horn's closed form on three
+ * correspondences inside RANSAC, one solver per (current keyframe, loop
+ * candidate), any number of solvers in one launch. */
+#define ORBSIM3_MAX_POINTS 2048      /* features per keyframe, correspondences per solver */
+#define ORBSIM3_MAX_ITERATIONS 320   /* hypotheses one call may run per solver */
+/* Sim3Solver::SetRansacParameters (:114-138) for n correspondences, on the
+ * host, no device needed: *out_max_its = mRansacMaxIts. log / pow are the
+ * platform's. A quotient that is not a finite int counts as INT_MIN, so
+ * max_its is 1. */
+int orbsim3_ransac_parameters(int n, double probability, int min_inliers, int max_iterations,
+                              int32_t* out_max_its);
+/* The constructor (:37-112) for one keyframe pair, on the host, no device
+ * needed. Inputs per feature i of keyframe 1 (n1 of them): matched12[i] = the
+ * index in keyframe 2 of the point matched to it (-1: no match, -2: a match
+ * whose point keyframe 2 does not observe), valid1[i] = the feature has a map
+ * point and it is not bad, xyz1[i][3] = its world position, octave1[i] =
+ * mvKeysUn[i].octave. Per feature j of keyframe 2 (n2): valid2[j] = its point
+ * is not bad, xyz2[j][3], octave2[j]. level_sigma2[nlevels] = mvLevelSigma2,
+ * Tcw1 / Tcw2 [16] row-major, the camera fx fy cx cy. Outputs, compacted in
+ * ascending i, room for n1 entries each: *n, indices1 = mvnIndices1, X3Dc1 /
+ * X3Dc2 [.][3], P1im1 / P2im2 [.][2], max_error1 / max_error2 = mvnMaxError1/2
+ * (9.210 * sigma2 truncated toward zero, as the reference's vector<size_t>
+ * holds it). ORBPL_ERR_ARG: n1 or n2 above ORBSIM3_MAX_POINTS, nlevels outside
+ * [1, 16], matched12 outside [-2, n2), an octave outside [0, nlevels). */
+typedef struct orbsim3_pair {
+  int32_t n1;
+  const int32_t* matched12;
+  const uint8_t* valid1;
+  const float* xyz1;
+  const int32_t* octave1;
+  int32_t n2;
+  const uint8_t* valid2;
+  const float* xyz2;
+  const int32_t* octave2;
+  const float* Tcw1;
+  const float* Tcw2;
+  float fx, fy, cx, cy;
+  int32_t* n;
+  int32_t* indices1;
+  float* X3Dc1;
+  float* X3Dc2;
+  float* P1im1;
+  float* P2im2;
+  int32_t* max_error1;
+  int32_t* max_error2;
+} orbsim3_pair;
+int orbsim3_setup(const orbsim3_pair* pairs, int npairs, const float* level_sigma2, int nlevels);
+/* The same in one launch over pitched device arrays, asynchronous on
+ * `stream`: pair s's keyframe-1 arrays and its outputs start at s * pitch1
+ * entries, its keyframe-2 arrays at s * pitch2, its poses at 16 s, its camera
+ * at 4 s. The outputs are the input arrays of orbsim3_device_batch with
+ * pt_pitch = pitch1. Counts are clamped to the pitches and the cap, octaves to
+ * [0, nlevels), and a matched12 entry outside [0, n2) is no match. */
+typedef struct orbsim3_setup_device_batch {
+  const int32_t* d_n1;
+  const int32_t* d_n2;
+  int32_t pitch1;
+  int32_t pitch2;
+  const int32_t* d_matched12;
+  const uint8_t* d_valid1;
+  const float* d_xyz1;
+  const int32_t* d_octave1;
+  const uint8_t* d_valid2;
+  const float* d_xyz2;
+  const int32_t* d_octave2;
+  const float* d_Tcw1;
+  const float* d_Tcw2;
+  const float* d_cam;
+  const float* d_level_sigma2;   /* [nlevels], shared by all pairs */
+  int32_t nlevels;
+  int32_t* d_n;
+  int32_t* d_indices1;
+  float* d_X3Dc1;
+  float* d_X3Dc2;
+  float* d_P1im1;
+  float* d_P2im2;
+  int32_t* d_max_error1;
+  int32_t* d_max_error2;
+} orbsim3_setup_device_batch;
+int orbsim3_setup_batch_device(const orbsim3_setup_device_batch* b, int npairs, void* stream);
+/* One solver. Inputs: the camera, the n compacted correspondences of
+ * orbsim3_setup, min_inliers (>= 3), max_its (orbsim3_ransac_parameters),
+ * fix_scale = mbFixScale, and n_draws raw rand() values in [0, RAND_MAX]:
+ * hypothesis k of a call uses draws[3k .. 3k+2], a call may run min(n_iterations,
+ * max_its - *iterations) hypotheses and n_draws must cover them. State, in/out,
+ * zero before the first call: *iterations = mnIterations, *best_inliers =
+ * mnBestInliers, best_mask[n] = mvbBestInliers, best_T12[16] = mBestT12,
+ * best_R[9] = mBestRotation, best_t[3] = mBestTranslation, *best_s =
+ * mBestScale. Outputs: T12[16] (row-major; all zero when *result == 0),
+ * *result (0 = empty cv::Mat, 1 = a Sim3), *no_more = bNoMore, *n_inliers,
+ * inliers[n] per compacted correspondence (the caller scatters them through
+ * mvnIndices1), *draws_consumed = 3 x the hypotheses the reference would have
+ * run before it returned. */
+typedef struct orbsim3_problem {
+  float fx, fy, cx, cy;
+  int32_t n;
+  const float* X3Dc1;
+  const float* X3Dc2;
+  const float* P1im1;
+  const float* P2im2;
+  const int32_t* max_error1;
+  const int32_t* max_error2;
+  int32_t min_inliers;
+  int32_t max_its;
+  int32_t fix_scale;
+  int32_t n_draws;
+  const int32_t* draws;
+  int32_t* iterations;
+  int32_t* best_inliers;
+  uint8_t* best_mask;
+  float* best_T12;
+  float* best_R;
+  float* best_t;
+  float* best_s;
+  float* T12;
+  int32_t* result;
+  int32_t* no_more;
+  int32_t* n_inliers;
+  uint8_t* inliers;
+  int32_t* draws_consumed;
+} orbsim3_problem;
+/* Sim3Solver::iterate(n_iterations, ...) for nsolvers independent solvers in
+ * one launch. ORBPL_ERR_ARG: n above ORBSIM3_MAX_POINTS, min_inliers below 3, a
+ * call that may run more than ORBSIM3_MAX_ITERATIONS hypotheses, or too few
+ * draws. */
+int orbsim3_iterate(const orbsim3_problem* problems, int nsolvers, int n_iterations);
+/* The same over pitched device arrays, asynchronous on `stream`: solver s's
+ * correspondences and masks start at s * pt_pitch entries, its draws at s *
+ * draw_pitch, its camera at d_cam + 4 s, its T12s at 16 s, best_R at 9 s,
+ * best_t at 3 s. n is clamped to the cap and the pitch, min_inliers below 3
+ * counts as 3, and the hypotheses of a call are clamped to
+ * ORBSIM3_MAX_ITERATIONS and to draw_pitch / 3. */
+typedef struct orbsim3_device_batch {
+  const int32_t* d_n;
+  const float* d_cam;
+  const float* d_X3Dc1;
+  const float* d_X3Dc2;
+  const float* d_P1im1;
+  const float* d_P2im2;
+  const int32_t* d_max_error1;
+  const int32_t* d_max_error2;
+  int32_t pt_pitch;
+  const int32_t* d_min_inliers;
+  const int32_t* d_max_its;
+  const int32_t* d_fix_scale;
+  const int32_t* d_draws;
+  int32_t draw_pitch;
+  int32_t* d_iterations;
+  int32_t* d_best_inliers;
+  uint8_t* d_best_mask;
+  float* d_best_T12;
+  float* d_best_R;
+  float* d_best_t;
+  float* d_best_s;
+  float* d_T12;
+  int32_t* d_result;
+  int32_t* d_no_more;
+  int32_t* d_n_inliers;
+  uint8_t* d_inliers;
+  int32_t* d_draws_consumed;
+} orbsim3_device_batch;
+int orbsim3_iterate_batch_device(const orbsim3_device_batch* b, int nsolvers, int n_iterations,
+                                 void* stream);
+
+/* ORBmatcher::SearchBySim3 (ORBmatcher.cc:1441-1693), batched
+ * over keyframe pairs: one launch, one workgroup per pair. Each keyframe's
+ * points are projected into the other through the Sim3 (s12, R12, t12), the
+ * best descriptor within the radius th * mvScaleFactors[level] and the octaves
+ * [level - 1, level] is taken on bestDist <= TH_HIGH (100), and a match is
+ * kept where both directions agree. reason1 / reason2 say, per feature and
+ * direction, where the reference left it: */
+#define ORBM_SIM3_MATCHED 0        /* vnMatch is set                           */
+#define ORBM_SIM3_NO_POINT 1       /* no map point, or a bad one               */
+#define ORBM_SIM3_ALREADY 2        /* vbAlreadyMatched                         */
+#define ORBM_SIM3_BEHIND 3         /* z < 0 in the other camera                */
+#define ORBM_SIM3_OUT_OF_IMAGE 4   /* !IsInImage(u, v) (also z == 0, NaN)      */
+#define ORBM_SIM3_DISTANCE 5       /* outside [0.8 min, 1.2 max]               */
+#define ORBM_SIM3_EMPTY_AREA 6     /* GetFeaturesInArea returned nothing       */
+#define ORBM_SIM3_NO_MATCH 7       /* bestDist > TH_HIGH (INT_MAX: all gated)  */
+#define ORBM_SIM3_MAX_FEATURES 2048
+/* One keyframe: kps_un = mvKeysUn (x, y, octave are read), desc[n][32] =
+ * mDescriptors, valid[n] = the feature has a map point and it is not bad, and
+ * of that point xyz[n][3], min_dist / max_dist[n] = raw mfMinDistance /
+ * mfMaxDistance (the 0.8f / 1.2f are applied inside), mp_desc[n][32] =
+ * GetDescriptor(); Tcw[16] row-major. */
+typedef struct orbm_sim3_keyframe {
+  int32_t n;
+  const orbpl_keypoint* kps_un;
+  const uint8_t* desc;
+  const uint8_t* valid;
+  const float* xyz;
+  const float* min_dist;
+  const float* max_dist;
+  const uint8_t* mp_desc;
+  const float* Tcw;
+} orbm_sim3_keyframe;
+/* matched12[n1], in/out, in the encoding of orbsim3_pair (the index in
+ * keyframe 2 of the matched point, -1 none, -2 a point keyframe 2 does not
+ * observe): written only where the reference writes vpMatches12. Outputs:
+ * *n_found, vn_match1[n1] / vn_match2[n2] = vnMatch1 / vnMatch2, reason1[n1] /
+ * reason2[n2]. */
+typedef struct orbm_sim3_pair {
+  orbm_sim3_keyframe kf1;
+  orbm_sim3_keyframe kf2;
+  float s12;
+  const float* R12;   /* [9] row-major */
+  const float* t12;   /* [3] */
+  int32_t* matched12;
+  int32_t* n_found;
+  int32_t* vn_match1;
+  int32_t* vn_match2;
+  int32_t* reason1;
+  int32_t* reason2;
+} orbm_sim3_pair;
+/* ORBPL_ERR_ARG: a keyframe with more than ORBM_SIM3_MAX_FEATURES features,
+ * nlevels outside [1, 16], a matched12 entry below -2 (one at or above n2 is a
+ * match that marks no feature of keyframe 2, as idx2 >= N2 in the reference). */
+int orbm_search_by_sim3(const orbpl_camera* cam, const float* scale_factors, int nlevels,
+                        const orbm_sim3_pair* pairs, int npairs, float th);
+/* The same over pitched device arrays, asynchronous on `stream`: pair p's
+ * keyframe-1 arrays start at p * pitch1 entries, its keyframe-2 arrays at p *
+ * pitch2, its poses at 16 p, R12 at 9 p, t12 at 3 p. Counts are clamped to the
+ * pitches; the pitches lie in [1, ORBM_SIM3_MAX_FEATURES]. */
+typedef struct orbm_sim3_device_batch {
+  const int32_t* d_n1;
+  const int32_t* d_n2;
+  int32_t pitch1;
+  int32_t pitch2;
+  const orbpl_keypoint* d_kps_un1;
+  const uint8_t* d_desc1;
+  const uint8_t* d_valid1;
+  const float* d_xyz1;
+  const float* d_min_dist1;
+  const float* d_max_dist1;
+  const uint8_t* d_mp_desc1;
+  const float* d_Tcw1;
+  const orbpl_keypoint* d_kps_un2;
+  const uint8_t* d_desc2;
+  const uint8_t* d_valid2;
+  const float* d_xyz2;
+  const float* d_min_dist2;
+  const float* d_max_dist2;
+  const uint8_t* d_mp_desc2;
+  const float* d_Tcw2;
+  const float* d_s12;
+  const float* d_R12;
+  const float* d_t12;
+  int32_t* d_matched12;
+  int32_t* d_n_found;
+  int32_t* d_vn_match1;
+  int32_t* d_vn_match2;
+  int32_t* d_reason1;
+  int32_t* d_reason2;
+} orbm_sim3_device_batch;
+int orbm_search_by_sim3_batch_device(const orbpl_camera* cam, const float* scale_factors,
+                                     int nlevels, const orbm_sim3_device_batch* b, int npairs,
+                                     float th, void* stream);
+
 /* ------------------------------------------------------------------------
  * Tracking::Relocalization (Tracking.cc:2049-2269) as one batched call over
  * many lost frames, each with its own keyframe database:
@@ -1588,6 +1846,15 @@ int lsdx_get_stages(lsdx_ctx* ctx, int frame, uint8_t* scaled, float* deg, uint3
 /* Test hook: the device replica of std::sort(records, key greater) on keys
  * in [0, 1023]; perm receives the record indices in sorted order. */
 int orbpl_test_introsort(const int32_t* keys, int n, int32_t* perm);
+/* Test hook, host only: ComputeSim3 on the three sampled points P1 / P2
+ * [3][3] (point c at 3 c) and CheckInliers over n correspondences with that
+ * hypothesis, through the header the kernel shares (sim3_core.h). err[n][2] =
+ * err1, err2. */
+int orbpl_test_sim3_hypothesis(const float* P1, const float* P2, int fix_scale, const float* cam,
+                               int n, const float* X3Dc1, const float* X3Dc2, const float* P1im1,
+                               const float* P2im2, const int32_t* max_error1,
+                               const int32_t* max_error2, float* R, float* t, float* s, float* T12,
+                               float* err, uint8_t* inliers);
 /* Debug: batch-mean shader-clock counters of the LSD seed loop of the last
  * run. Speculative loop (default): growing cycles, rounds, speculative
  * regions, total cycles, fit + refinement cycles, validate + commit

@@ -456,6 +456,14 @@ def _declare_track(L):
                                            vp, vp, vp]
     L.orbpnp_iterate.argtypes = [vp, i, i]
     L.orbpnp_iterate_batch_device.argtypes = [vp, i, i, vp]
+    L.orbsim3_ransac_parameters.argtypes = [i, C.c_double, i, i, vp]
+    L.orbsim3_setup.argtypes = [vp, i, vp, i]
+    L.orbsim3_setup_batch_device.argtypes = [vp, i, vp]
+    L.orbsim3_iterate.argtypes = [vp, i, i]
+    L.orbsim3_iterate_batch_device.argtypes = [vp, i, i, vp]
+    L.orbpl_test_sim3_hypothesis.argtypes = [vp, vp, i, vp, i] + [vp] * 12
+    L.orbm_search_by_sim3.argtypes = [vp, vp, i, vp, i, C.c_float]
+    L.orbm_search_by_sim3_batch_device.argtypes = [vp, vp, i, vp, i, C.c_float, vp]
 
 
 _declare_orig = _declare
@@ -592,6 +600,20 @@ class ORBmatcher:
             int(ORBdist), int(self.checkOri), _ptr(match), C.byref(nm)),
             "orbm_search_by_projection_kf")
         return match[:n].copy(), nm.value
+
+    def SearchBySim3(self, camera, scale_factors, kf1, kf2, matched12, s12, R12, t12, th):
+        """SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)
+        (ORBmatcher.cc:1441-1693). ``kf1`` / ``kf2``: dicts as for
+        search_by_sim3_batch. ``matched12`` (int32 [n1], the index in keyframe
+        2 of the matched point, -1 none, -2 not observed by keyframe 2) is
+        updated in place. Returns nFound; the per-feature record of the call
+        is left in ``self.last_sim3``."""
+        o = search_by_sim3_batch(camera, scale_factors,
+                                 [dict(kf1=kf1, kf2=kf2, matched12=matched12, s12=s12, R12=R12,
+                                       t12=t12)], th)[0]
+        matched12[...] = o["matched12"]
+        self.last_sim3 = o
+        return o["n_found"]
 
 
 def stereo_matches(camera, left, right, kl, dl, kr, dr, frame=0):
@@ -1745,6 +1767,488 @@ class PnpDeviceProblems:
                      draws_consumed=int(dc[s]),
                      state=dict(iterations=int(it[s]), best_inliers=int(bi[s]),
                                 best_mask=bm[s, :self.n[s]].copy(), best_Tcw=bT[s].copy()))
+                for s in range(self.ns)]
+
+
+# ---------------------------------------------------------------------------
+# Sim3Solver (Sim3Solver.cc)
+# ---------------------------------------------------------------------------
+SIM3_MAX_POINTS = 2048
+SIM3_MAX_ITERATIONS = 320
+_SIM3_CORR = (("X3Dc1", np.float32, 3), ("X3Dc2", np.float32, 3), ("P1im1", np.float32, 2),
+              ("P2im2", np.float32, 2), ("max_error1", np.int32, 1), ("max_error2", np.int32, 1))
+_SIM3_STATE = (("best_T12", 16), ("best_R", 9), ("best_t", 3), ("best_s", 1))
+
+
+class Sim3Pair(C.Structure):
+    _fields_ = ([("n1", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("matched12", "valid1", "xyz1", "octave1")] +
+                [("n2", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("valid2", "xyz2", "octave2", "Tcw1", "Tcw2")] +
+                [(k, C.c_float) for k in ("fx", "fy", "cx", "cy")] +
+                [(k, C.c_void_p) for k in ("n", "indices1", "X3Dc1", "X3Dc2", "P1im1", "P2im2",
+                                           "max_error1", "max_error2")])
+
+
+class Sim3SetupDeviceBatch(C.Structure):
+    _fields_ = ([("d_n1", C.c_void_p), ("d_n2", C.c_void_p), ("pitch1", C.c_int32),
+                 ("pitch2", C.c_int32)] +
+                [("d_" + k, C.c_void_p) for k in ("matched12", "valid1", "xyz1", "octave1",
+                                                  "valid2", "xyz2", "octave2", "Tcw1", "Tcw2",
+                                                  "cam", "level_sigma2")] +
+                [("nlevels", C.c_int32)] +
+                [("d_" + k, C.c_void_p) for k in ("n", "indices1", "X3Dc1", "X3Dc2", "P1im1",
+                                                  "P2im2", "max_error1", "max_error2")])
+
+
+class Sim3Problem(C.Structure):
+    _fields_ = ([(k, C.c_float) for k in ("fx", "fy", "cx", "cy")] + [("n", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("X3Dc1", "X3Dc2", "P1im1", "P2im2", "max_error1",
+                                           "max_error2")] +
+                [(k, C.c_int32) for k in ("min_inliers", "max_its", "fix_scale", "n_draws")] +
+                [(k, C.c_void_p) for k in ("draws", "iterations", "best_inliers", "best_mask",
+                                           "best_T12", "best_R", "best_t", "best_s", "T12",
+                                           "result", "no_more", "n_inliers", "inliers",
+                                           "draws_consumed")])
+
+
+class Sim3DeviceBatch(C.Structure):
+    _fields_ = ([("d_" + k, C.c_void_p) for k in ("n", "cam", "X3Dc1", "X3Dc2", "P1im1", "P2im2",
+                                                  "max_error1", "max_error2")] +
+                [("pt_pitch", C.c_int32)] +
+                [("d_" + k, C.c_void_p) for k in ("min_inliers", "max_its", "fix_scale", "draws")] +
+                [("draw_pitch", C.c_int32)] +
+                [("d_" + k, C.c_void_p) for k in ("iterations", "best_inliers", "best_mask",
+                                                  "best_T12", "best_R", "best_t", "best_s", "T12",
+                                                  "result", "no_more", "n_inliers", "inliers",
+                                                  "draws_consumed")])
+
+
+def sim3_ransac_parameters(N, probability=0.99, minInliers=6, maxIterations=300):
+    """Sim3Solver::SetRansacParameters (:114-138) on the host, with the
+    platform's log / pow: mRansacMaxIts for N correspondences."""
+    out = np.zeros(1, np.int32)
+    check(lib().orbsim3_ransac_parameters(int(N), float(probability), int(minInliers),
+                                          int(maxIterations), _ptr(out)),
+          "orbsim3_ransac_parameters")
+    return int(out[0])
+
+
+def _sim3_pair_arrays(pr):
+    f32, i32, u8 = np.float32, np.int32, np.uint8
+    a = dict(matched12=_c(pr["matched12"], i32).reshape(-1), valid1=_c(pr["valid1"], u8).reshape(-1),
+             xyz1=_c(pr["xyz1"], f32).reshape(-1, 3), octave1=_c(pr["octave1"], i32).reshape(-1),
+             valid2=_c(pr["valid2"], u8).reshape(-1), xyz2=_c(pr["xyz2"], f32).reshape(-1, 3),
+             octave2=_c(pr["octave2"], i32).reshape(-1), Tcw1=_c(pr["Tcw1"], f32).reshape(16),
+             Tcw2=_c(pr["Tcw2"], f32).reshape(16))
+    n1, n2 = len(a["matched12"]), len(a["valid2"])
+    if any(len(a[k]) != n1 for k in ("valid1", "xyz1", "octave1")) or \
+            any(len(a[k]) != n2 for k in ("xyz2", "octave2")):
+        raise OrbplError("per-feature arrays of a keyframe differ in length")
+    cam = pr["cam"]
+    if hasattr(cam, "fx"):
+        cam = (cam.fx, cam.fy, cam.cx, cam.cy)
+    return a, n1, n2, [float(np.float32(c)) for c in cam]
+
+
+def sim3_setup(pairs, level_sigma2):
+    """The Sim3Solver constructor (:37-112) on the host for a list of keyframe
+    pairs. Each pair is a dict: ``matched12`` [n1] (index in keyframe 2 of the
+    point matched to feature i; -1 no match, -2 a point keyframe 2 does not
+    observe), ``valid1`` [n1], ``xyz1`` [n1, 3], ``octave1`` [n1], ``valid2``
+    [n2], ``xyz2`` [n2, 3], ``octave2`` [n2], ``Tcw1``, ``Tcw2`` [4, 4],
+    ``cam`` = (fx, fy, cx, cy). Returns per pair a dict: ``n``, ``indices1``,
+    ``X3Dc1``, ``X3Dc2``, ``P1im1``, ``P2im2``, ``max_error1``, ``max_error2``."""
+    sig = _c(level_sigma2, np.float32).reshape(-1)
+    arr = (Sim3Pair * max(1, len(pairs)))()
+    keep, outs = [], []
+    for p, pr in enumerate(pairs):
+        a, n1, n2, cam = _sim3_pair_arrays(pr)
+        o = dict(n=np.zeros(1, np.int32), indices1=np.zeros(max(1, n1), np.int32))
+        for k, dt, w in _SIM3_CORR:
+            o[k] = np.zeros((max(1, n1), w) if w > 1 else max(1, n1), dt)
+        keep += [a, o]
+        arr[p] = Sim3Pair(n1, _ptr(a["matched12"]), _ptr(a["valid1"]), _ptr(a["xyz1"]),
+                          _ptr(a["octave1"]), n2, _ptr(a["valid2"]), _ptr(a["xyz2"]),
+                          _ptr(a["octave2"]), _ptr(a["Tcw1"]), _ptr(a["Tcw2"]), *cam,
+                          _ptr(o["n"]), _ptr(o["indices1"]),
+                          *[_ptr(o[k]) for k, _, _ in _SIM3_CORR])
+        outs.append(o)
+    check(lib().orbsim3_setup(C.byref(arr), len(pairs), _ptr(sig), len(sig)), "orbsim3_setup")
+    res = []
+    for o in outs:
+        n = int(o["n"][0])
+        res.append(dict(n=n, **{k: v[:n].copy() for k, v in o.items() if k != "n"}))
+    return res
+
+
+def sim3_hypotheses(n, min_inliers, max_its, iterations, n_iterations):
+    """hypotheses iterate(n_iterations) runs at most from this state: a call
+    needs 3 draws for each"""
+    if n < min_inliers:
+        return 0
+    return max(0, min(n_iterations, max_its - iterations))
+
+
+def sim3_new_state(n):
+    return dict(iterations=0, best_inliers=0, best_mask=np.zeros(n, np.uint8),
+                best_T12=np.zeros((4, 4), np.float32), best_R=np.zeros((3, 3), np.float32),
+                best_t=np.zeros(3, np.float32), best_s=np.float32(0))
+
+
+def sim3_iterate_batch(problems, n_iterations):
+    """Sim3Solver::iterate(n_iterations) for a list of independent solvers in
+    one launch. Each problem is a dict: ``cam`` = (fx, fy, cx, cy), ``corr`` =
+    the compacted correspondences of sim3_setup, ``min_inliers``, ``max_its``
+    (sim3_ransac_parameters), ``fix_scale``, ``draws`` = raw rand() values, 3
+    per hypothesis the call may run (sim3_hypotheses), ``state`` = the dict the
+    previous call returned (missing or None: a new solver). Returns per problem
+    a dict: ``result`` (0 empty, 1 a Sim3), ``no_more``, ``n_inliers``,
+    ``inliers`` bool[n] per compacted correspondence, ``T12`` float32[4, 4],
+    ``draws_consumed``, ``state``."""
+    ns = len(problems)
+    arr = (Sim3Problem * max(1, ns))()
+    keep, outs = [], []
+    f32, i32 = np.float32, np.int32
+    for p, pr in enumerate(problems):
+        co = pr["corr"]
+        c = [_c(co[k], dt).reshape((-1, w) if w > 1 else -1) for k, dt, w in _SIM3_CORR]
+        n = len(c[0])
+        if any(len(x) != n for x in c):
+            raise OrbplError("correspondence arrays differ in length")
+        dr = _c(pr["draws"], i32).reshape(-1)
+        st = pr.get("state") or sim3_new_state(n)
+        it = np.array([st["iterations"]], i32)
+        bi = np.array([st["best_inliers"]], i32)
+        bm = _c(st["best_mask"], np.uint8).copy()
+        if len(bm) != n:
+            raise OrbplError("state belongs to another problem")
+        sv = [_c(st[k], f32).reshape(w).copy() for k, w in _SIM3_STATE]
+        T = np.zeros(16, f32)
+        res, nm, ni, dc = (np.zeros(1, i32) for _ in range(4))
+        inl = np.zeros(max(1, n), np.uint8)
+        cam = [float(x) for x in pr["cam"]]
+        keep += [c, dr, it, bi, bm, sv, T, res, nm, ni, dc, inl]
+        arr[p] = Sim3Problem(cam[0], cam[1], cam[2], cam[3], n, *[_ptr(x) for x in c],
+                             int(pr["min_inliers"]), int(pr["max_its"]),
+                             int(bool(pr["fix_scale"])), len(dr), _ptr(dr), _ptr(it), _ptr(bi),
+                             _ptr(bm), *[_ptr(x) for x in sv], _ptr(T), _ptr(res), _ptr(nm),
+                             _ptr(ni), _ptr(inl), _ptr(dc))
+        outs.append((n, it, bi, bm, sv, T, res, nm, ni, dc, inl))
+    check(lib().orbsim3_iterate(C.byref(arr), ns, int(n_iterations)), "orbsim3_iterate")
+    return [dict(result=int(res[0]), no_more=bool(nm[0]), n_inliers=int(ni[0]),
+                 inliers=inl[:n].astype(bool), T12=T.reshape(4, 4).copy(),
+                 draws_consumed=int(dc[0]),
+                 state=dict(iterations=int(it[0]), best_inliers=int(bi[0]), best_mask=bm,
+                            best_T12=sv[0].reshape(4, 4), best_R=sv[1].reshape(3, 3),
+                            best_t=sv[2], best_s=np.float32(sv[3][0])))
+            for n, it, bi, bm, sv, T, res, nm, ni, dc, inl in outs]
+
+
+class Sim3Solver:
+    """ORB_SLAM2::Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale) over a
+    keyframe pair as sim3_setup takes it. Draws come from the C library's
+    rand() through the process-wide look-ahead queue PnPsolver uses (P29)."""
+
+    def __init__(self, pair, level_sigma2, bFixScale=False):
+        _, self.mN1, _, self.cam = _sim3_pair_arrays(pair)
+        self.corr = sim3_setup([pair], level_sigma2)[0]
+        self.N = self.corr["n"]
+        self.mvnIndices1 = self.corr["indices1"]
+        self.fix_scale = bool(bFixScale)
+        self.state = sim3_new_state(self.N)
+        self.SetRansacParameters()
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
+        if minInliers < 3:
+            raise OrbplError("minInliers below the minimal set of 3")
+        self.min_inliers = int(minInliers)
+        self.max_its = sim3_ransac_parameters(self.N, probability, minInliers, maxIterations)
+        self.state["iterations"] = 0
+
+    def iterate(self, nIterations, draws=None):
+        """Returns (T12 float32[4, 4] or None, bNoMore, vbInliers bool per
+        feature of keyframe 1, nInliers). ``draws`` = raw rand() values for
+        this call (3 per hypothesis it may run); None takes them from rand()."""
+        need = 3 * sim3_hypotheses(self.N, self.min_inliers, self.max_its,
+                                   self.state["iterations"], nIterations)
+        own = draws is None
+        d = _pnp_take_rand(need) if own else _c(draws, np.int32)
+        o = sim3_iterate_batch([dict(cam=self.cam, corr=self.corr, min_inliers=self.min_inliers,
+                                     max_its=self.max_its, fix_scale=self.fix_scale, draws=d,
+                                     state=self.state)], nIterations)[0]
+        if own:
+            del _pnp_rand_queue[:o["draws_consumed"]]
+        self.state = o["state"]
+        self.last = o
+        vb = np.zeros(self.mN1, bool)
+        if o["result"]:
+            vb[self.mvnIndices1[o["inliers"]]] = True
+        return (o["T12"] if o["result"] else None), o["no_more"], vb, o["n_inliers"]
+
+    def find(self, draws=None):
+        """(T12 or None, vbInliers12, nInliers)"""
+        T, _, vb, n = self.iterate(self.max_its, draws)
+        return T, vb, n
+
+    def GetEstimatedRotation(self):
+        return self.state["best_R"].copy()
+
+    def GetEstimatedTranslation(self):
+        return self.state["best_t"].copy()
+
+    def GetEstimatedScale(self):
+        return np.float32(self.state["best_s"])
+
+
+class Sim3DeviceProblems:
+    """The pitched device arrays of orbsim3_setup_batch_device and
+    orbsim3_iterate_batch_device for a list of keyframe pairs (dicts as for
+    sim3_setup, plus ``fix_scale``, ``draws`` and optionally ``min_inliers``):
+    setup() runs the constructor kernel and the host parameter table,
+    iterate() launches on the null stream without a host round trip,
+    download() synchronises and returns the correspondences, the outputs and
+    the state as sim3_setup and sim3_iterate_batch do."""
+
+    def __init__(self, pairs, level_sigma2, probability=0.99, minInliers=6, maxIterations=300,
+                 draw_pitch=3 * SIM3_MAX_ITERATIONS, device=0):
+        f32, i32, u8 = np.float32, np.int32, np.uint8
+        self.ns = ns = len(pairs)
+        self.device, self.draw_pitch = device, int(draw_pitch)
+        self.params = (probability, maxIterations)
+        S = max(1, ns)
+        arrs = [_sim3_pair_arrays(p) for p in pairs]
+        self.n1 = np.array([a[1] for a in arrs] or [0], i32)
+        self.n2 = np.array([a[2] for a in arrs] or [0], i32)
+        self.pitch1 = p1 = max(1, int(self.n1.max()))
+        self.pitch2 = p2 = max(1, int(self.n2.max()))
+        sig = _c(level_sigma2, f32).reshape(-1)
+        h = dict(n1=self.n1, n2=self.n2, matched12=np.full((S, p1), -1, i32),
+                 valid1=np.zeros((S, p1), u8), xyz1=np.zeros((S, p1, 3), f32),
+                 octave1=np.zeros((S, p1), i32), valid2=np.zeros((S, p2), u8),
+                 xyz2=np.zeros((S, p2, 3), f32), octave2=np.zeros((S, p2), i32),
+                 Tcw1=np.zeros((S, 16), f32), Tcw2=np.zeros((S, 16), f32),
+                 cam=np.zeros((S, 4), f32), level_sigma2=sig,
+                 min_inliers=np.full(S, int(minInliers), i32), fix_scale=np.zeros(S, i32),
+                 draws=np.zeros((S, self.draw_pitch), i32))
+        for s, ((a, n1, n2, cam), p) in enumerate(zip(arrs, pairs)):
+            for k in ("matched12", "valid1", "xyz1", "octave1"):
+                h[k][s, :n1] = a[k]
+            for k in ("valid2", "xyz2", "octave2"):
+                h[k][s, :n2] = a[k]
+            h["Tcw1"][s], h["Tcw2"][s], h["cam"][s] = a["Tcw1"], a["Tcw2"], cam
+            h["min_inliers"][s] = p.get("min_inliers", minInliers)
+            h["fix_scale"][s] = bool(p.get("fix_scale", False))
+            d = _c(p.get("draws", ()), i32).reshape(-1)[:self.draw_pitch]
+            h["draws"][s, :len(d)] = d
+        self.nlevels = len(sig)
+        z = dict(n=np.zeros(S, i32), indices1=np.zeros((S, p1), i32), max_its=np.ones(S, i32),
+                 iterations=np.zeros(S, i32), best_inliers=np.zeros(S, i32),
+                 best_mask=np.zeros((S, p1), u8), T12=np.zeros((S, 16), f32),
+                 result=np.zeros(S, i32), no_more=np.zeros(S, i32), n_inliers=np.zeros(S, i32),
+                 inliers=np.zeros((S, p1), u8), draws_consumed=np.zeros(S, i32))
+        for k, dt, w in _SIM3_CORR:
+            z[k] = np.zeros((S, p1, w), dt)
+        for k, w in _SIM3_STATE:
+            z[k] = np.zeros((S, w), f32)
+        self.bufs = b = {k: DeviceBuffer.from_array(v, device) for k, v in {**h, **z}.items()}
+        self.setup_batch = Sim3SetupDeviceBatch(
+            b["n1"].ptr, b["n2"].ptr, p1, p2,
+            *[b[k].ptr for k in ("matched12", "valid1", "xyz1", "octave1", "valid2", "xyz2",
+                                 "octave2", "Tcw1", "Tcw2", "cam", "level_sigma2")],
+            self.nlevels,
+            *[b[k].ptr for k in ("n", "indices1", "X3Dc1", "X3Dc2", "P1im1", "P2im2",
+                                 "max_error1", "max_error2")])
+        self.batch = Sim3DeviceBatch(
+            *[b[k].ptr for k in ("n", "cam", "X3Dc1", "X3Dc2", "P1im1", "P2im2", "max_error1",
+                                 "max_error2")], p1,
+            *[b[k].ptr for k in ("min_inliers", "max_its", "fix_scale", "draws")],
+            self.draw_pitch,
+            *[b[k].ptr for k in ("iterations", "best_inliers", "best_mask", "best_T12", "best_R",
+                                 "best_t", "best_s", "T12", "result", "no_more", "n_inliers",
+                                 "inliers", "draws_consumed")])
+        self.min_inliers = h["min_inliers"]
+        self.n = None
+
+    def setup(self, stream=None):
+        """the constructor kernel, then SetRansacParameters per solver on the
+        host (it needs each N): one synchronisation"""
+        check(lib().orbsim3_setup_batch_device(C.byref(self.setup_batch), self.ns, stream),
+              "orbsim3_setup_batch_device")
+        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
+        S = max(1, self.ns)
+        self.n = self.bufs["n"].download(np.int32, S)
+        mx = np.ones(S, np.int32)
+        for s in range(self.ns):
+            mx[s] = sim3_ransac_parameters(self.n[s], self.params[0], self.min_inliers[s],
+                                           self.params[1])
+        self.max_its = mx
+        self.bufs["max_its"].upload(mx)
+
+    def iterate(self, n_iterations, stream=None):
+        check(lib().orbsim3_iterate_batch_device(C.byref(self.batch), self.ns, int(n_iterations),
+                                                 stream), "orbsim3_iterate_batch_device")
+
+    def download(self):
+        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
+        S, p1, b = max(1, self.ns), self.pitch1, self.bufs
+        i32, f32 = np.int32, np.float32
+        g = {k: b[k].download(i32, S) for k in ("n", "result", "no_more", "n_inliers",
+                                                "draws_consumed", "iterations", "best_inliers")}
+        ind = b["indices1"].download(i32, (S, p1))
+        inl, bm = (b[k].download(np.uint8, (S, p1)) for k in ("inliers", "best_mask"))
+        co = {k: b[k].download(dt, (S, p1, w)) for k, dt, w in _SIM3_CORR}
+        sv = {k: b[k].download(f32, (S, w)) for k, w in _SIM3_STATE}
+        T = b["T12"].download(f32, (S, 4, 4))
+        out = []
+        for s in range(self.ns):
+            n = int(g["n"][s])
+            corr = dict(n=n, indices1=ind[s, :n].copy())
+            for k, dt, w in _SIM3_CORR:
+                corr[k] = co[k][s, :n].reshape((n, w) if w > 1 else n).copy()
+            out.append(dict(corr=corr, result=int(g["result"][s]), no_more=bool(g["no_more"][s]),
+                            n_inliers=int(g["n_inliers"][s]), inliers=inl[s, :n].astype(bool),
+                            T12=T[s].copy(), draws_consumed=int(g["draws_consumed"][s]),
+                            state=dict(iterations=int(g["iterations"][s]),
+                                       best_inliers=int(g["best_inliers"][s]),
+                                       best_mask=bm[s, :n].copy(),
+                                       best_T12=sv["best_T12"][s].reshape(4, 4).copy(),
+                                       best_R=sv["best_R"][s].reshape(3, 3).copy(),
+                                       best_t=sv["best_t"][s].copy(),
+                                       best_s=np.float32(sv["best_s"][s, 0]))))
+        return out
+
+
+# ---------------------------------------------------------------------------
+# ORBmatcher::SearchBySim3 (ORBmatcher.cc:1441-1693; DESIGN.md P58)
+# ---------------------------------------------------------------------------
+SIM3_MATCHED, SIM3_NO_POINT, SIM3_ALREADY, SIM3_BEHIND, SIM3_OUT_OF_IMAGE, SIM3_DISTANCE, \
+    SIM3_EMPTY_AREA, SIM3_NO_MATCH = range(8)
+SIM3_MAX_FEATURES = 2048
+_SBS_KF = (("kps_un", KP_DTYPE, ()), ("desc", np.uint8, (32,)), ("valid", np.uint8, ()),
+           ("xyz", np.float32, (3,)), ("min_dist", np.float32, ()), ("max_dist", np.float32, ()),
+           ("mp_desc", np.uint8, (32,)))
+
+
+class Sim3Keyframe(C.Structure):
+    _fields_ = [("n", C.c_int32)] + [(k, C.c_void_p) for k, _, _ in _SBS_KF] + [("Tcw", C.c_void_p)]
+
+
+class Sim3MatchPair(C.Structure):
+    _fields_ = ([("kf1", Sim3Keyframe), ("kf2", Sim3Keyframe), ("s12", C.c_float)] +
+                [(k, C.c_void_p) for k in ("R12", "t12", "matched12", "n_found", "vn_match1",
+                                           "vn_match2", "reason1", "reason2")])
+
+
+class Sim3MatchDeviceBatch(C.Structure):
+    _fields_ = ([("d_n1", C.c_void_p), ("d_n2", C.c_void_p), ("pitch1", C.c_int32),
+                 ("pitch2", C.c_int32)] +
+                [("d_%s%d" % (k, s), C.c_void_p) for s in (1, 2)
+                 for k in [k for k, _, _ in _SBS_KF] + ["Tcw"]] +
+                [("d_" + k, C.c_void_p) for k in ("s12", "R12", "t12", "matched12", "n_found",
+                                                  "vn_match1", "vn_match2", "reason1", "reason2")])
+
+
+def _sbs_keyframe(kf):
+    a = {k: _c(kf[k], dt).reshape((-1,) + w) for k, dt, w in _SBS_KF}
+    n = len(a["kps_un"])
+    if any(len(v) != n for v in a.values()):
+        raise OrbplError("per-feature arrays of a keyframe differ in length")
+    a["Tcw"] = _c(kf["Tcw"], np.float32).reshape(16)
+    return a, n
+
+
+def search_by_sim3_batch(camera, scale_factors, pairs, th):
+    """ORBmatcher::SearchBySim3 for a list of keyframe pairs in one launch.
+    Each pair is a dict: ``kf1`` / ``kf2`` = dicts of per-feature arrays
+    ``kps_un`` (KP_DTYPE), ``desc`` [n, 32], ``valid`` (the feature has a map
+    point and it is not bad), ``xyz`` [n, 3], ``min_dist`` / ``max_dist`` (raw
+    mfMinDistance / mfMaxDistance), ``mp_desc`` [n, 32], and ``Tcw`` [4, 4];
+    ``matched12`` [n1]; ``s12``, ``R12`` [3, 3], ``t12`` [3]. Returns per pair
+    a dict: ``n_found``, ``matched12`` (updated copy), ``vn_match1``,
+    ``vn_match2``, ``reason1``, ``reason2`` (SIM3_* codes)."""
+    sf = _c(scale_factors, np.float32)
+    arr = (Sim3MatchPair * max(1, len(pairs)))()
+    keep, outs = [], []
+    i32 = np.int32
+    for p, pr in enumerate(pairs):
+        a1, n1 = _sbs_keyframe(pr["kf1"])
+        a2, n2 = _sbs_keyframe(pr["kf2"])
+        m = _c(pr["matched12"], i32).reshape(-1).copy()
+        if len(m) != n1:
+            raise OrbplError("matched12 and keyframe 1 differ in length")
+        R, t = _c(pr["R12"], np.float32).reshape(9), _c(pr["t12"], np.float32).reshape(3)
+        nf = np.zeros(1, i32)
+        v1, r1 = np.zeros(max(1, n1), i32), np.zeros(max(1, n1), i32)
+        v2, r2 = np.zeros(max(1, n2), i32), np.zeros(max(1, n2), i32)
+        keep += [a1, a2, m, R, t, nf, v1, v2, r1, r2]
+        k1 = Sim3Keyframe(n1, *[_ptr(a1[k]) for k, _, _ in _SBS_KF], _ptr(a1["Tcw"]))
+        k2 = Sim3Keyframe(n2, *[_ptr(a2[k]) for k, _, _ in _SBS_KF], _ptr(a2["Tcw"]))
+        arr[p] = Sim3MatchPair(k1, k2, float(pr["s12"]), _ptr(R), _ptr(t), _ptr(m), _ptr(nf),
+                               _ptr(v1), _ptr(v2), _ptr(r1), _ptr(r2))
+        outs.append((n1, n2, m, nf, v1, v2, r1, r2))
+    check(lib().orbm_search_by_sim3(C.byref(camera), _ptr(sf), len(sf), C.byref(arr), len(pairs),
+                                    float(th)), "orbm_search_by_sim3")
+    return [dict(n_found=int(nf[0]), matched12=m, vn_match1=v1[:n1], vn_match2=v2[:n2],
+                 reason1=r1[:n1], reason2=r2[:n2]) for n1, n2, m, nf, v1, v2, r1, r2 in outs]
+
+
+class Sim3MatchDeviceProblems:
+    """The pitched device arrays of orbm_search_by_sim3_batch_device for a list
+    of pairs (dicts as for search_by_sim3_batch): run() launches without a
+    host round trip, download() synchronises and returns what
+    search_by_sim3_batch returns."""
+
+    def __init__(self, pairs, device=0):
+        f32, i32 = np.float32, np.int32
+        self.ns = ns = len(pairs)
+        self.device = device
+        S = max(1, ns)
+        ks = [(_sbs_keyframe(p["kf1"]), _sbs_keyframe(p["kf2"])) for p in pairs]
+        self.n1 = np.array([k[0][1] for k in ks] or [0], i32)
+        self.n2 = np.array([k[1][1] for k in ks] or [0], i32)
+        self.pitch = pt = (max(1, int(self.n1.max())), max(1, int(self.n2.max())))
+        h = dict(n1=self.n1, n2=self.n2, s12=np.zeros(S, f32), R12=np.zeros((S, 9), f32),
+                 t12=np.zeros((S, 3), f32), matched12=np.full((S, pt[0]), -1, i32))
+        for side in (1, 2):
+            for k, dt, w in _SBS_KF:
+                h["%s%d" % (k, side)] = np.zeros((S, pt[side - 1]) + w, dt)
+            h["Tcw%d" % side] = np.zeros((S, 16), f32)
+        for s, (p, kk) in enumerate(zip(pairs, ks)):
+            for side, (a, n) in zip((1, 2), kk):
+                for k, _, _ in _SBS_KF:
+                    h["%s%d" % (k, side)][s, :n] = a[k]
+                h["Tcw%d" % side][s] = a["Tcw"]
+            h["s12"][s] = p["s12"]
+            h["R12"][s] = _c(p["R12"], f32).reshape(9)
+            h["t12"][s] = _c(p["t12"], f32).reshape(3)
+            h["matched12"][s, :self.n1[s]] = _c(p["matched12"], i32).reshape(-1)
+        self.host_matched12 = h["matched12"]     # to restore the in/out array between runs
+        z = dict(n_found=np.zeros(S, i32), vn_match1=np.zeros((S, pt[0]), i32),
+                 vn_match2=np.zeros((S, pt[1]), i32), reason1=np.zeros((S, pt[0]), i32),
+                 reason2=np.zeros((S, pt[1]), i32))
+        self.bufs = b = {k: DeviceBuffer.from_array(v, device) for k, v in {**h, **z}.items()}
+        self.batch = Sim3MatchDeviceBatch(
+            b["n1"].ptr, b["n2"].ptr, pt[0], pt[1],
+            *[b["%s%d" % (k, s)].ptr for s in (1, 2) for k in [k for k, _, _ in _SBS_KF] + ["Tcw"]],
+            *[b[k].ptr for k in ("s12", "R12", "t12", "matched12", "n_found", "vn_match1",
+                                 "vn_match2", "reason1", "reason2")])
+
+    def run(self, camera, scale_factors, th, stream=None):
+        sf = _c(scale_factors, np.float32)
+        check(lib().orbm_search_by_sim3_batch_device(C.byref(camera), _ptr(sf), len(sf),
+                                                     C.byref(self.batch), self.ns, float(th),
+                                                     stream), "orbm_search_by_sim3_batch_device")
+
+    def download(self):
+        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
+        S, pt, b, i32 = max(1, self.ns), self.pitch, self.bufs, np.int32
+        nf = b["n_found"].download(i32, S)
+        m, v1, r1 = (b[k].download(i32, (S, pt[0])) for k in ("matched12", "vn_match1", "reason1"))
+        v2, r2 = (b[k].download(i32, (S, pt[1])) for k in ("vn_match2", "reason2"))
+        return [dict(n_found=int(nf[s]), matched12=m[s, :self.n1[s]].copy(),
+                     vn_match1=v1[s, :self.n1[s]].copy(), vn_match2=v2[s, :self.n2[s]].copy(),
+                     reason1=r1[s, :self.n1[s]].copy(), reason2=r2[s, :self.n2[s]].copy())
                 for s in range(self.ns)]
 
 

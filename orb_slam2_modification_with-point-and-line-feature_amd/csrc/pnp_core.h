@@ -467,11 +467,13 @@ PNP_HD inline int random_int(int raw, int size, double rand_max_p1) {
   return (int)(((double)raw / rand_max_p1) * size);
 }
 
-// The four indices hypothesis draws d[0..3] pick from mvAllIndices = 0..N-1
-// with the swap-with-back removal (:188-201), N >= 4.
-PNP_HD inline void sample4(const int* d, int N, double rand_max_p1, int* idx) {
-  int pos[4], val[4], nov = 0;
-  for (int i = 0; i < 4; i++) {
+// The K indices hypothesis draws d[0..K-1] pick from mvAllIndices = 0..N-1
+// with the swap-with-back removal (:188-201; Sim3Solver.cc:163-177 with K = 3),
+// N >= K.
+template <int K>
+PNP_HD inline void sample_k(const int* d, int N, double rand_max_p1, int* idx) {
+  int pos[K], val[K], nov = 0;
+  for (int i = 0; i < K; i++) {
     const int size = N - i;
     int r = random_int(d[i], size, rand_max_p1);
     r = r < 0 ? 0 : (r > size - 1 ? size - 1 : r);  // raw values outside [0, RAND_MAX]
@@ -485,6 +487,9 @@ PNP_HD inline void sample4(const int* d, int N, double rand_max_p1, int* idx) {
     val[nov] = back;
     nov++;
   }
+}
+PNP_HD inline void sample4(const int* d, int N, double rand_max_p1, int* idx) {
+  sample_k<4>(d, N, rand_max_p1, idx);
 }
 
 }  // namespace pnp
