@@ -243,7 +243,9 @@ typedef struct orbpl_match_last {
 
 /* match[i] = index j of the last-frame map point assigned to current keypoint
  * i (CurrentFrame.mvpMapPoints[i] = LastFrame.mvpMapPoints[j]) or -1.
- * *nmatches = the function's return value. */
+ * *nmatches = the function's return value. Refused: more than 2048 keypoints
+ * in either frame, NULL arrays of a frame that has keypoints, a keypoint octave
+ * of either frame outside [0, nlevels) ("keypoint octave outside the pyramid"). */
 int orbm_search_by_projection_last(const orbpl_camera* cam, const float* scale_factors,
                                    int nlevels, const orbpl_match_current* cur,
                                    const orbpl_match_last* last, float th, int mono,
@@ -285,7 +287,8 @@ int orbpl_frame_is_in_frustum(const orbpl_camera* cam, float scale_factor, int n
  * NULL: none); keypoints holding one with Observations() > 0 are skipped, as
  * are keypoints claimed during the call. match[i] = index of the last local
  * map point assigned to keypoint i in this call (the reference overwrites
- * F.mvpMapPoints[i]), -1 = unchanged. *nmatches = return value. */
+ * F.mvpMapPoints[i]), -1 = unchanged. *nmatches = return value. Refused: a
+ * level of an in-view point or a keypoint octave outside [0, nlevels). */
 int orbm_search_by_projection_local(const orbpl_camera* cam, const float* scale_factors,
                                     int nlevels, const orbpl_match_current* cur, int nmp,
                                     const uint8_t* in_view, const float* proj_x,

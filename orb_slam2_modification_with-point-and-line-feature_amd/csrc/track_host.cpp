@@ -120,6 +120,18 @@ int orbm_search_by_projection_last(const orbpl_camera* cam, const float* scale_f
   TrackConsts c;
   int rc = make_consts(cam, scale_factors, nullptr, nlevels, &c);
   if (rc) return rc;
+  if (!cur->Tcw || !last->Tcw || (n > 0 && (!cur->kps_un || !cur->desc || !cur->uright)) ||
+      (nl > 0 && (!last->kps_un || !last->has_mp || !last->outlier || !last->mp_xyz ||
+                  !last->mp_desc || !last->mp_nobs)))
+    return arg_fail("NULL frame arrays");
+  // the kernel reads scale[] at a last-frame octave and keeps the current
+  // octaves as int8 for the level window
+  for (int i = 0; i < n; i++)
+    if (cur->kps_un[i].octave < 0 || cur->kps_un[i].octave >= nlevels)
+      return arg_fail("keypoint octave outside the pyramid");
+  for (int i = 0; i < nl; i++)
+    if (last->kps_un[i].octave < 0 || last->kps_un[i].octave >= nlevels)
+      return arg_fail("keypoint octave outside the pyramid");
   const int P = std::max(1, std::max(n, nl));
   float T[32];   // the current pose, then the last frame's
   memcpy(T, cur->Tcw, 64);
@@ -272,6 +284,10 @@ int orbm_search_by_projection_local(const orbpl_camera* cam, const float* scale_
   TrackConsts c;
   int rc = make_consts(cam, scale_factors, nullptr, nlevels, &c);
   if (rc) return rc;
+  // the kernel sorts the keypoints into per-octave buckets
+  for (int i = 0; i < n; i++)
+    if (cur->kps_un[i].octave < 0 || cur->kps_un[i].octave >= nlevels)
+      return arg_fail("keypoint octave outside the pyramid");
   const int P = std::max(1, n), M = std::max(1, nmp);
   HostStage st;
   LocalArgs a{};

@@ -214,9 +214,13 @@ def three_maxima(hist):
 
 
 def search_by_projection_kf(frame, cur_has_mp, kf_angle, kf_valid, kf_found, mp_xyz, mp_min_dist,
-                            mp_max_dist, mp_desc, th, orb_dist, check_ori):
+                            mp_max_dist, mp_desc, th, orb_dist, check_ori, trace=None):
     """Returns (match, nmatches): match[i] = keyframe feature whose map point
-    the call put into CurrentFrame.mvpMapPoints[i], else -1."""
+    the call put into CurrentFrame.mvpMapPoints[i], else -1. trace (a dict, for
+    the tests' non-vacuity checks) receives points[i] = (ncand, skipped, taken):
+    the keypoints of the window not held on entry with distance <= orb_dist, how
+    many of them a point of this call held when point i chose, the keypoint it
+    took or -1; and, with check_ori, hist (bin sizes) and keep (the kept bins)."""
     F = frame
     n = len(F.kps)
     holds = [bool(h) for h in cur_has_mp]      # CurrentFrame.mvpMapPoints[i] != NULL
@@ -264,12 +268,20 @@ def search_by_projection_kf(frame, cur_has_mp, kf_angle, kf_valid, kf_found, mp_
         if not idx:
             continue
         best_dist, best_idx = 256, -1
+        ncand = skipped = 0
         for i2 in idx:
+            if trace is not None and not cur_has_mp[i2] and \
+                    _hamming(mp_desc[i], F.desc[i2]) <= orb_dist:
+                ncand += 1
+                skipped += holds[i2]
             if holds[i2]:
                 continue
             d = _hamming(mp_desc[i], F.desc[i2])
             if d < best_dist:
                 best_dist, best_idx = d, i2
+        if trace is not None:
+            taken = best_idx if best_dist <= orb_dist else -1
+            trace.setdefault("points", {})[i] = (ncand, skipped, taken)
         if best_dist <= orb_dist and best_idx >= 0:
             holds[best_idx] = True
             match[best_idx] = i
@@ -284,6 +296,8 @@ def search_by_projection_kf(frame, cur_has_mp, kf_angle, kf_valid, kf_found, mp_
                 hist[b].append(best_idx)
     if check_ori:
         i1, i2, i3 = three_maxima(hist)
+        if trace is not None:
+            trace.update(hist=[len(h) for h in hist], keep=(i1, i2, i3))
         for b in range(30):
             if b != i1 and b != i2 and b != i3:
                 for j in hist[b]:

@@ -48,8 +48,8 @@ def cur(n=0, Tcw=Z, kps_un=Z, desc=Z, uright=Z):
     return ref(orbpl.MatchCurrent(n, Tcw, kps_un, desc, uright))
 
 
-def last(n=0):
-    return ref(orbpl.MatchLast(n, Z, Z, Z, Z, Z, Z, Z))
+def last(n=0, kps_un=Z):
+    return ref(orbpl.MatchLast(n, Z, kps_un, Z, Z, Z, Z, Z))
 
 
 def pose(n=0, nl=0, kps_un=Z, kl_obs=Z, nlevels=8):
@@ -154,6 +154,18 @@ ROWS = [
     ("orbm_search_by_projection_last", "nl_2049", {4: lambda: last(2049)}, CAP_KP),
     ("orbm_search_by_projection_last", "nlevels_0", {2: 0}, "nlevels out of range"),
     ("orbm_search_by_projection_last", "nlevels_17", {2: 17}, "nlevels out of range"),
+    ("orbm_search_by_projection_last", "null_current_arrays", {3: lambda: cur(1, desc=None)},
+     "NULL frame arrays"),
+    ("orbm_search_by_projection_last", "null_pose", {3: lambda: cur(0, Tcw=None)},
+     "NULL frame arrays"),
+    ("orbm_search_by_projection_last", "current_octave_8",
+     {3: lambda: cur(2, kps_un=octaves(7, 8))}, "keypoint octave outside the pyramid"),
+    ("orbm_search_by_projection_last", "current_octave_negative",
+     {3: lambda: cur(2, kps_un=octaves(0, -1))}, "keypoint octave outside the pyramid"),
+    ("orbm_search_by_projection_last", "last_octave_8",
+     {4: lambda: last(2, kps_un=octaves(7, 8))}, "keypoint octave outside the pyramid"),
+    ("orbm_search_by_projection_last", "last_octave_negative",
+     {4: lambda: last(2, kps_un=octaves(0, -1))}, "keypoint octave outside the pyramid"),
 
     ("orbpl_pose_optimization", "null_pose", {2: None}, "NULL argument"),
     ("orbpl_pose_optimization", "negative_n", {1: lambda: pose(-1, 0)},
@@ -197,6 +209,10 @@ ROWS = [
     ("orbm_search_by_projection_local", "level_out_of_range",
      {4: 2, 5: lambda: u8(1, 1), 9: lambda: ints(0, 8)}, "level out of range"),
     ("orbm_search_by_projection_local", "nlevels_0", {2: 0}, "nlevels out of range"),
+    ("orbm_search_by_projection_local", "octave_8", {3: lambda: cur(2, kps_un=octaves(7, 8))},
+     "keypoint octave outside the pyramid"),
+    ("orbm_search_by_projection_local", "octave_negative",
+     {3: lambda: cur(2, kps_un=octaves(0, -1))}, "keypoint octave outside the pyramid"),
 
     ("orbpl_line_frame_prepare", "null_camera", {0: None}, "bad argument"),
     ("orbpl_line_frame_prepare", "negative_n", {2: -1}, "bad argument"),
