@@ -1796,6 +1796,17 @@ int orbl_search_by_projection_pairs(const orbpl_camera* cam, const float* Tcw, i
  * has no match (pinned: the reference reads past the end). nq <= 256. */
 int orbl_match_bf_knn(int nq, const uint8_t* qdesc, int nt, const uint8_t* tdesc, int32_t* out,
                       int* nmatches);
+/* Stereo line end-point depths, the defined mode P17 of DESIGN.md (the
+ * reference's stereo Frame extracts no lines): left line i takes the right
+ * line with the smallest LBD Hamming distance (the first on ties) among those
+ * passing, in this order, Hamming <= 45, |angle difference| <= 10 degrees,
+ * min / max length >= 0.45f, both lines non-horizontal (|dy| >= 0.25 length),
+ * row overlap >= 0.5 of the shorter row span and both end-point disparities in
+ * (0, bf / mb). dstart / dend = bf / disparity, -1 without a match. kl / kr:
+ * the left / right (rectified) KeyLines with their LBD rows; nl, nr <= 80. */
+int orbl_stereo_line_depths(const orbpl_camera* cam, const orbpl_keyline* kl, const uint8_t* desc,
+                            int nl, const orbpl_keyline* kr, const uint8_t* desc_r, int nr,
+                            float* dstart, float* dend);
 
 /* ------------------------------------------------------------------------
  * Hamming distance — ORBmatcher::DescriptorDistance (ORBmatcher.cc:2083-2103)

@@ -429,6 +429,7 @@ def _declare_track(L):
     L.orbl_search_by_projection_pairs.argtypes = [vp, vp, i, i, vp, vp, vp, i, vp, vp, vp, vp, vp,
                                                   vp, vp, ip, vp, i, ip, vp, ip, ip]
     L.orbl_match_bf_knn.argtypes = [i, vp, i, vp, vp, ip]
+    L.orbl_stereo_line_depths.argtypes = [vp, vp, vp, i, vp, vp, i, vp, vp]
     L.orbpl_tracker_get_status.argtypes = [vp, vp, vp, vp, vp]
     L.orbpl_tracker_get_lines.argtypes = [vp, i, vp, vp, vp, vp, ip]
     L.orbpl_tracker_line_timings.argtypes = [vp, i, vp, ip]
@@ -781,6 +782,20 @@ def line_is_in_frustum(Tcw, ml_xyz6):
     check(lib().orbl_frame_is_in_frustum(_ptr(T), len(X), _ptr(X), _ptr(out)),
           "orbl_frame_is_in_frustum")
     return out
+
+
+def stereo_line_depths(camera, kl, desc, kr, desc_r):
+    """Stereo line end-point depths (orbl_stereo_line_depths):
+    (depth_start, depth_end) of the left lines, -1 without a match."""
+    kl = np.ascontiguousarray(kl, KEYLINE_DTYPE)
+    kr = np.ascontiguousarray(kr, KEYLINE_DTYPE)
+    d = np.ascontiguousarray(desc, np.uint8)
+    dr = np.ascontiguousarray(desc_r, np.uint8)
+    nl = len(kl)
+    ds, de = np.zeros(max(1, nl), np.float32), np.zeros(max(1, nl), np.float32)
+    check(lib().orbl_stereo_line_depths(C.byref(camera), _ptr(kl), _ptr(d), nl, _ptr(kr), _ptr(dr),
+                                        len(kr), _ptr(ds), _ptr(de)), "orbl_stereo_line_depths")
+    return ds[:nl].copy(), de[:nl].copy()
 
 
 def _line_search_list(camera, Tcw, cur_kl_un, cur_desc, cur_nobs, valid, ml_xyz6, ml_desc):

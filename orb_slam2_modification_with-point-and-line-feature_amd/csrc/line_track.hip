@@ -362,7 +362,7 @@ __global__ void __launch_bounds__(128) k_stereo_lines(TrackConsts c, StereoLineA
   const uint4 a0 = da[0], a1 = da[1];
   float bs = -1.0f, be = -1.0f;
   const double ady = (double)ka.endPointY - ka.startPointY;
-  if (fabs(ady) >= 0.25 * ka.lineLength) {
+  if (!(fabs(ady) < 0.25 * ka.lineLength)) {   // as the oracle writes it: a NaN length is not flat
     const double ay0 = smin(ka.startPointY, ka.endPointY), ay1 = smax(ka.startPointY, ka.endPointY);
     int best = 46;
     for (int j = 0; j < nr; j++) {

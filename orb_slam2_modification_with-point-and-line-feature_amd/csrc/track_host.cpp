@@ -724,4 +724,35 @@ int orbl_match_bf_knn(int nq, const uint8_t* qdesc, int nt, const uint8_t* tdesc
   return st.rc();
 }
 
+int orbl_stereo_line_depths(const orbpl_camera* cam, const orbpl_keyline* kl, const uint8_t* desc,
+                            int nl, const orbpl_keyline* kr, const uint8_t* desc_r, int nr,
+                            float* dstart, float* dend) {
+  if (!cam || nl < 0 || nr < 0) return arg_fail("bad argument");
+  if (nl > kLineKeep || nr > kLineKeep)
+    return arg_fail("more key lines than LineExtractor keeps (80)");
+  if ((nl > 0 && (!kl || !desc || !dstart || !dend)) || (nr > 0 && (!kr || !desc_r)))
+    return arg_fail("NULL line arrays");
+  TrackConsts c;
+  int rc = make_consts(cam, nullptr, nullptr, 1, &c);
+  if (rc) return rc;
+  if (nl == 0) return ORBPL_OK;
+  const int L = kLineKeep;
+  HostStage st;
+  StereoLineArgs a{};
+  a.nl = st.in_value(nl);
+  a.kl = st.in(kl, nl, L);
+  a.desc = st.in(desc, 32 * nl, 32 * L);
+  a.nr = st.in_value(nr);
+  a.kr = st.in(kr, nr, L);
+  a.desc_r = st.in(desc_r, 32 * nr, 32 * L);
+  a.dstart = st.out<float>(L);
+  a.dend = st.out<float>(L);
+  if (st.rc()) return st.rc();
+  launch_stereo_lines(c, a, 1, scratch_stream());
+  st.launched();
+  st.back(dstart, a.dstart, nl);
+  st.back(dend, a.dend, nl);
+  return st.rc();
+}
+
 }  // extern "C"

@@ -274,6 +274,35 @@ def test_line_match_bf_knn(O, nq, nt):
     assert nm.value == en and np.array_equal(out[:nt], eo) and kept(out, nt)
 
 
+def steep_lines(n, shift):
+    """the segment (300, 200)-(320, 260) moved `shift` pixels to the left"""
+    k = keylines(n)
+    k["startPointX"] = k["sPointInOctaveX"] = 300.0 - shift
+    k["endPointX"] = k["ePointInOctaveX"] = 320.0 - shift
+    k["endPointY"] = k["ePointInOctaveY"] = 260.0
+    k["angle"] = math.atan2(60.0, 20.0)
+    k["lineLength"] = math.hypot(20.0, 60.0)
+    return k
+
+
+@pytest.mark.parametrize("nl,nr", COUNTS)
+def test_stereo_line_depths(O, nl, nr):
+    """the right line is the left one 10 pixels to the left: both depths are
+    bf / 10"""
+    cam, cam_o = cams(O)
+    kl, kr = steep_lines(nl, 0.0), steep_lines(nr, 10.0)
+    dl, dr = DESC[:nl].copy(), DESC[:nr].copy()
+    eds, ede = O.stereo_line_depths(cam_o, kl, dl, kr, dr)
+    ds, de = sent(nl + 2, np.float32), sent(nl + 2, np.float32)
+    check_ok(orbpl.lib().orbl_stereo_line_depths(
+        C.byref(cam), p(kl), p(dl), nl, p(kr), p(dr), nr, p(ds) if nl else None,
+        p(de) if nl else None), "stereo_line_depths")
+    assert np.array_equal(ds[:nl], eds) and np.array_equal(de[:nl], ede)
+    assert kept(ds, nl) and kept(de, nl)
+    if nl:
+        assert ds[0] == de[0] == (4.0 if nr else -1.0)
+
+
 # ---------------------------------------------------------------------------
 # Frame
 # ---------------------------------------------------------------------------

@@ -125,6 +125,7 @@ GOOD = {
     "orbl_search_by_projection_pairs": lambda: [cam(), Z, 0, 0, Z, Z, Z, 0, Z, Z, Z, Z, Z, Z, Z, Z,
                                                 Z, 0, Z, Z, Z, Z],
     "orbl_match_bf_knn": lambda: [0, Z, 0, Z, Z, Z],
+    "orbl_stereo_line_depths": lambda: [cam(), Z, Z, 0, Z, Z, 0, Z, Z],
     "orbkf_detect_reloc": lambda: [kfdb(), 1, 0],
     "orbpnp_iterate": lambda: [pnp(), 1, 1],
     "orblm_create_new_map_features": lambda: [cam(), Z, Z, 8, lm_problem(), 1],
@@ -287,6 +288,17 @@ ROWS = [
     ("orbl_match_bf_knn", "nq_257", {0: 257}, "more than 256 query descriptors"),
     ("orbl_match_bf_knn", "null_queries", {0: 1, 1: None}, "NULL descriptor arrays"),
     ("orbl_match_bf_knn", "null_output", {2: 1, 4: None}, "NULL descriptor arrays"),
+
+    ("orbl_stereo_line_depths", "null_camera", {0: None}, "bad argument"),
+    ("orbl_stereo_line_depths", "negative_nl", {3: -1}, "bad argument"),
+    ("orbl_stereo_line_depths", "negative_nr", {6: -1}, "bad argument"),
+    ("orbl_stereo_line_depths", "nl_81", {3: 81}, CAP_KL),
+    ("orbl_stereo_line_depths", "nr_81", {6: 81}, CAP_KL),
+    ("orbl_stereo_line_depths", "null_left_lines", {3: 1, 1: None}, "NULL line arrays"),
+    ("orbl_stereo_line_depths", "null_left_descriptors", {3: 1, 2: None}, "NULL line arrays"),
+    ("orbl_stereo_line_depths", "null_output", {3: 1, 8: None}, "NULL line arrays"),
+    ("orbl_stereo_line_depths", "null_right_lines", {6: 1, 4: None}, "NULL line arrays"),
+    ("orbl_stereo_line_depths", "null_right_descriptors", {6: 1, 5: None}, "NULL line arrays"),
 
     ("orbkf_detect_reloc", "scoring_1", {2: 1},
      "only the vocabulary's L1 scoring (L1_NORM = 0) is built"),
