@@ -51,11 +51,12 @@ def lib():
         if not LIB_PATH.exists():
             raise OrbplError(f"{LIB_PATH} not built; run __graft_entry__.build() or make -C csrc")
         _lib = C.CDLL(str(LIB_PATH))
-        _declare(_lib)
+        for declare in _DECLARE:
+            declare(_lib)
     return _lib
 
 
-def _declare(L):
+def _declare_core(L):
     vp, i, ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
     L.orbpl_last_error.restype = C.c_char_p
     L.orbpl_version.restype = C.c_char_p
@@ -465,14 +466,6 @@ def _declare_track(L):
     L.orbpl_test_sim3_hypothesis.argtypes = [vp, vp, i, vp, i] + [vp] * 12
     L.orbm_search_by_sim3.argtypes = [vp, vp, i, vp, i, C.c_float]
     L.orbm_search_by_sim3_batch_device.argtypes = [vp, vp, i, vp, i, C.c_float, vp]
-
-
-_declare_orig = _declare
-
-
-def _declare(L):  # noqa: F811
-    _declare_orig(L)
-    _declare_track(L)
 
 
 def _c(a, dt):
@@ -1142,11 +1135,8 @@ KEYLINE_DTYPE = np.dtype([("angle", "<f4"), ("class_id", "<i4"), ("octave", "<i4
                           ("ePointInOctaveY", "<f4"), ("lineLength", "<f4"),
                           ("numOfPixels", "<i4")])
 
-_declare_points = _declare
 
-
-def _declare(L):  # noqa: F811
-    _declare_points(L)
+def _declare_lines(L):
     vp, i, ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
     L.lsdx_create.argtypes = [i, i, i, i, C.POINTER(vp)]
     L.lsdx_destroy.argtypes = [vp]
@@ -1300,14 +1290,6 @@ def _declare_voc(L):
     L.orbv_transform.argtypes = [vp, i, vp, i, i, vp, vp, ip, vp]
     L.orbv_transform_batch_device.argtypes = [vp, vp, C.c_int64, vp, i, i, i, vp, vp, vp, vp, vp,
                                               vp, C.c_int64, vp, vp]
-
-
-_declare_prev_voc = _declare
-
-
-def _declare(L):  # noqa: F811
-    _declare_prev_voc(L)
-    _declare_voc(L)
 
 
 class ORBVocabulary:
@@ -2301,14 +2283,6 @@ def _declare_reloc(L):
     L.orbrl_relocalize.argtypes = [vp, vp, i, i]
 
 
-_declare_before_reloc = _declare
-
-
-def _declare(L):  # noqa: F811
-    _declare_before_reloc(L)
-    _declare_reloc(L)
-
-
 def reloc_ransac_table(n_entries=RL_TABLE_N + 1):
     """SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991)'s (min_inliers,
     max_its) for N = 0 .. n_entries - 1, as the Relocalizer's handle holds it."""
@@ -2478,14 +2452,6 @@ def _declare_reloc_device(L):
                                                 C.c_void_p]
 
 
-_declare_before_reloc_device = _declare
-
-
-def _declare(L):  # noqa: F811
-    _declare_before_reloc_device(L)
-    _declare_reloc_device(L)
-
-
 def _reloc_relocalize_batch_device(self, batch, n, scoring=0, stream=None):
     """orbrl_relocalize_batch_device over a RelocDeviceBatch of n problems"""
     check(lib().orbrl_relocalize_batch_device(self._h, C.byref(batch), int(n), int(scoring),
@@ -2542,14 +2508,6 @@ def _declare_localmap(L):
     L.orbm_search_for_triangulation.argtypes = [vp, vp, vp, i, vp, vp, vp, i, i, vp,
                                                 C.POINTER(C.c_int), vp]
     L.orbl_search_for_triangulation.argtypes = [i, vp, i, vp, vp, C.POINTER(C.c_int)]
-
-
-_declare_before_localmap = _declare
-
-
-def _declare(L):  # noqa: F811
-    _declare_before_localmap(L)
-    _declare_localmap(L)
 
 
 def _lm_arrays(kf):
@@ -2800,14 +2758,6 @@ def _declare_fuse(L):
     L.orblm_debug_search_in_neighbors_phases.argtypes = [vp, vp, vp, i, vp, i, vp, vp]
 
 
-_declare_before_fuse = _declare
-
-
-def _declare(L):  # noqa: F811
-    _declare_before_fuse(L)
-    _declare_fuse(L)
-
-
 def _sin_ordered(kf):
     o = [int(x) for x in kf.get("ordered", ())][:LM_MAX_MAP_KF]
     return np.array(o + [-1] * (LM_MAX_MAP_KF - len(o)), np.int32)
@@ -2911,58 +2861,110 @@ def fuse(camera, scale_factors, level_sigma2, map_, kf, points, th=3.0):
     return NeighborFuser(camera, scale_factors, level_sigma2).fuse(map_, kf, points, th)
 
 
-class SinDeviceProblems:
+class MapPools:
+    """The maps of a list of problems flattened into pooled host arrays (self.host)
+    in the layout csrc/map_pool.h states: problem s is the row self.prob[s] =
+    (kf0, nkf, mp0, nmp, problem[last]), what no map fills is padding (_PAD, else
+    0). No library call before alloc(), which makes the device copies (self.bufs)."""
+
+    # column: (key in a keyframe's dict, dtype, shape of a keyframe's row; "P": the pitch)
+    _KF = dict(id=("id", np.int32, ()), n=("n", np.int32, ()), T=("Tcw", np.float32, (16,)),
+               kps_un=("kps_un", KP_DTYPE, ("P",)), uright=("uright", np.float32, ("P",)),
+               kdesc=("desc", np.uint8, ("P", 32)), mp=("mp", np.int32, ("P",)),
+               ordered=("ordered", np.int32, (LM_MAX_MAP_KF,)))
+    _PT = {name: (dt, (w,) if w > 1 else ()) for name, dt, w in _SIN_POINT_IO + _SIN_POINT_OUT}
+    _PAD = dict(uright=-1, mp=-1, ordered=-1, bad=1, depth=-1, parent=-1)
+
+    def __init__(self, problems, last, kf_cols, pt_cols):
+        self.ns = len(problems)
+        self.parts = [_sin_map_arrays(p["map"]) for p in problems]
+        prob, k0, m0 = [], 0, 0
+        for (kfs, M, _), p in zip(self.parts, problems):
+            prob.append([k0, len(kfs), m0, M, int(p[last])])
+            k0, m0 = k0 + len(kfs), m0 + M
+        self.prob = np.array(prob or [[0, 0, 0, 0, 0]], np.int32)
+        self.K, self.M = max(1, k0), max(1, m0)
+        self.pitch = max([1] + [k["n"] for kfs, _, _ in self.parts for k in kfs])
+        self.host = {}
+        for c in kf_cols:
+            key, dt, row = self._KF[c]
+            a = self.column(c, self.K, tuple(self.pitch if x == "P" else x for x in row), dt)
+            for g, k in enumerate(k for kfs, _, _ in self.parts for k in kfs):
+                a[(g, slice(k["n"])) if "P" in row else g] = k[key]
+        for c in pt_cols:
+            a = self.column(c, self.M, *self._PT[c][::-1])
+            for (_, Mp, pts), row in zip(self.parts, prob):
+                a[row[2]:row[2] + Mp] = pts[c]
+
+    def column(self, c, rows, shape, dt):
+        """a new host column, all padding"""
+        a = self.host[c] = np.zeros((rows,) + shape, dt)
+        if c in self._PAD:
+            a[...] = self._PAD[c]
+        return a
+
+    def alloc(self, device, result, **nbytes):
+        """device copies of the host columns, the table, a zeroed error flag, one
+        `result` per problem and uninitialised buffers of the given sizes"""
+        self.device, self.result = device, result
+        mk = lambda a: DeviceBuffer.from_array(a, device)
+        b = self.bufs = {k: mk(v) for k, v in self.host.items()}
+        b.update(prob=mk(self.prob), err=mk(np.zeros(1, np.int32)),
+                 result=DeviceBuffer(max(1, self.ns) * C.sizeof(result), device))
+        b.update({c: DeviceBuffer(n, device) for c, n in nbytes.items()})
+        return b
+
+    def upload(self):
+        for name in self._IO:
+            self.bufs[name].upload(self.host[name])
+
+    def fetch(self, error, pt_cols, kf_cols=()):
+        """synchronises; per problem: the map's arrays with the device's slots and
+        named point columns, the named keyframe columns' rows, the result struct"""
+        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
+        if int(self.bufs["err"].download(np.int32, 1)[0]):
+            raise OrbplError(error)
+
+        def get(c):
+            if c in self.host:
+                return self.bufs[c].download(self.host[c].dtype, self.host[c].shape)
+            return self.bufs[c].download(self._PT[c][0], (self.M,) + self._PT[c][1])   # an out column
+        mp, pt, kf = get("mp"), {c: get(c) for c in pt_cols}, {c: get(c) for c in kf_cols}
+        sz = C.sizeof(self.result)
+        res = self.bufs["result"].download(np.uint8, max(1, self.ns) * sz).tobytes()
+        outs = []
+        for s, ((kfs, Mp, pts), (k0, nk, m0, _, _)) in enumerate(zip(self.parts, self.prob)):
+            out = {name: v.copy() for name, v in pts.items()}
+            out.update({c: v[m0:m0 + Mp].copy() for c, v in pt.items()})
+            out["mp"] = [mp[k0 + j, :k["n"]].copy() for j, k in enumerate(kfs)]
+            outs.append((out, {c: v[k0:k0 + nk].copy() for c, v in kf.items()},
+                         self.result.from_buffer_copy(res[s * sz:(s + 1) * sz])))
+        return outs
+
+
+class SinDeviceProblems(MapPools):
     """The device pools of orblm_search_in_neighbors_batch_device for a list of
     problems (as NeighborFuser.search_in_neighbors takes them): run() launches
     without a host round trip, download() synchronises and returns the same
     per-problem results. Every problem owns its range of the pools. A run
-    mutates the pools: upload() restores the inputs."""
+    mutates the pools: upload() restores the inputs. device=None: host arrays only."""
+
+    _KF_COLS = ("id", "n", "T", "kps_un", "uright", "kdesc", "mp", "ordered")
+    _PT_COLS = tuple(n for n, _, _ in _SIN_POINT_IO)
+    _PT_OUT = tuple(n for n, _, _ in _SIN_POINT_OUT)
+    _IO = ("mp",) + _PT_COLS
 
     def __init__(self, fuser, problems, device=0):
-        self.fuser, self.device, self.ns = fuser, device, len(problems)
-        self.parts = [_sin_map_arrays(p["map"]) for p in problems]
-        prob, k0, m0 = [], 0, 0
-        for (kfs, M, _), p in zip(self.parts, problems):
-            prob.append([k0, len(kfs), m0, M, int(p["cur"])])
-            k0, m0 = k0 + len(kfs), m0 + M
-        self.prob = np.array(prob or [[0, 0, 0, 0, 0]], np.int32)
-        self.K, self.M = max(1, k0), max(1, m0)
-        self.pitch = P = max([1] + [k["n"] for kfs, _, _ in self.parts for k in kfs])
-        self.list_pitch = L = max([P] + [M for _, M, _ in self.parts])
-        K, M, S = self.K, self.M, max(1, self.ns)
-        h = self.host = dict(id=np.zeros(K, np.int32), n=np.zeros(K, np.int32), T=np.zeros((K, 16), np.float32),
-                             kps_un=np.zeros((K, P), KP_DTYPE), uright=np.full((K, P), -1, np.float32),
-                             kdesc=np.zeros((K, P, 32), np.uint8), mp=np.full((K, P), -1, np.int32),
-                             ordered=np.full((K, LM_MAX_MAP_KF), -1, np.int32))
-        for name, dt, w in _SIN_POINT_IO:
-            h[name] = np.zeros((M, w) if w > 1 else (M,), dt)
-        h["bad"][:] = 1
-        for (kfs, Mp, pts), row in zip(self.parts, prob):
-            for j, k in enumerate(kfs):
-                g, n = row[0] + j, k["n"]
-                h["id"][g], h["n"][g], h["T"][g], h["ordered"][g] = k["id"], n, k["Tcw"], k["ordered"]
-                h["kps_un"][g, :n], h["uright"][g, :n] = k["kps_un"], k["uright"]
-                h["kdesc"][g, :n], h["mp"][g, :n] = k["desc"], k["mp"]
-            for name, _, _ in _SIN_POINT_IO:
-                h[name][row[2]:row[2] + Mp] = pts[name]
-        mk = lambda a: DeviceBuffer.from_array(a, device)
-        b = self.bufs = {k: mk(v) for k, v in h.items()}
-        b.update(prob=mk(self.prob), replaced_by=DeviceBuffer(M * 4, device), n_obs=DeviceBuffer(M * 4, device),
-                 obs=DeviceBuffer(M * LM_MAX_MAP_KF * 2, device), desc_src=DeviceBuffer(M * 8, device),
-                 mark=DeviceBuffer(M, device), result=DeviceBuffer(S * C.sizeof(LmSinResult), device),
-                 list=DeviceBuffer(S * L * 4, device), search=DeviceBuffer(S * L * 4, device),
-                 err=mk(np.zeros(1, np.int32)))
-        self.batch = LmSinDeviceBatch(
-            K, P, M, L, *[b[k].ptr for k in (
-                "prob", "id", "n", "T", "kps_un", "uright", "kdesc", "mp", "ordered", "xyz", "normal",
-                "min_dist", "max_dist", "desc", "ref_kf", "bad", "n_visible", "n_found", "replaced_by",
-                "n_obs", "obs", "desc_src", "mark", "result", "list", "search", "err")])
-
-    def upload(self):
-        for name in ("mp",) + tuple(n for n, _, _ in _SIN_POINT_IO):
-            a = self.host[name]
-            check(lib().orbpl_memcpy_htod(self.device, self.bufs[name].ptr, _ptr(a), a.nbytes),
-                  "orbpl_memcpy_htod")
+        super().__init__(problems, "cur", self._KF_COLS, self._PT_COLS)
+        self.fuser = fuser
+        self.list_pitch = L = max([self.pitch] + [M for _, M, _ in self.parts])
+        if device is not None:
+            M, SL = self.M, max(1, self.ns) * L * 4
+            b = self.alloc(device, LmSinResult, replaced_by=M * 4, n_obs=M * 4, obs=M * LM_MAX_MAP_KF * 2,
+                           desc_src=M * 8, mark=M, list=SL, search=SL)
+            self.batch = LmSinDeviceBatch(self.K, self.pitch, M, L, *[b[k].ptr for k in (
+                ("prob",) + self._KF_COLS + self._PT_COLS + self._PT_OUT +
+                ("mark", "result", "list", "search", "err"))])
 
     def run(self, stream=None):
         check(lib().orblm_search_in_neighbors_batch_device(
@@ -2981,22 +2983,8 @@ class SinDeviceProblems:
         return ticks.download(np.int64, (max(1, self.ns), 3))[:self.ns] / 100.0
 
     def download(self):
-        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
-        b, K, M, P = self.bufs, self.K, self.M, self.pitch
-        if int(b["err"].download(np.int32, 1)[0]):
-            raise OrbplError("orblm_search_in_neighbors_batch_device: candidate list overflow")
-        mp = b["mp"].download(np.int32, (K, P))
-        pool = {name: b[name].download(dt, (M, w) if w > 1 else (M,))
-                for name, dt, w in _SIN_POINT_IO + _SIN_POINT_OUT}
-        res = np.frombuffer(b["result"].download(np.uint8, max(1, self.ns) * C.sizeof(LmSinResult)).tobytes(),
-                            np.uint8)
-        outs = []
-        for s, ((kfs, Mp, _), row) in enumerate(zip(self.parts, self.prob)):
-            out = {name: pool[name][row[2]:row[2] + Mp].copy() for name in pool}
-            out["mp"] = [mp[row[0] + j, :k["n"]].copy() for j, k in enumerate(kfs)]
-            r = LmSinResult.from_buffer_copy(res[s * C.sizeof(LmSinResult):(s + 1) * C.sizeof(LmSinResult)].tobytes())
-            outs.append(_sin_result_out(out, r))
-        return outs
+        return [_sin_result_out(out, r) for out, _, r in self.fetch(
+            "orblm_search_in_neighbors_batch_device: candidate list overflow", self._PT_COLS + self._PT_OUT)]
 
 
 # ---------------------------------------------------------------------------
@@ -3046,14 +3034,6 @@ def _declare_cull(L):
     L.orblm_keyframe_culling.argtypes = [vp, i, vp, i]
     L.orblm_keyframe_culling_batch_device.argtypes = [vp, vp, i, vp]
     L.orblm_cull_recent.argtypes = [i, vp, i]
-
-
-_declare_before_cull = _declare
-
-
-def _declare(L):  # noqa: F811
-    _declare_before_cull(L)
-    _declare_cull(L)
 
 
 def _kfc_graph_arrays(prob, kfs):
@@ -3168,84 +3148,53 @@ class MapCuller:
         return outs
 
 
-class KfcDeviceProblems:
+class KfcDeviceProblems(MapPools):
     """The device pools of orblm_keyframe_culling_batch_device for a list of
-    problems (as MapCuller.keyframes takes them): SinDeviceProblems' layout for the
-    keyframes and points, plus depth at kp_pitch and the graph arrays (conn_w
-    rows at a pitch of 64). MapCuller.keyframes_device(pools) launches without a
-    host round trip, download() synchronises and returns the same per-problem
-    results. A run mutates the pools: upload() restores the inputs."""
+    problems (as MapCuller.keyframes takes them): the map's pools, plus depth at
+    kp_pitch and the graph arrays (conn_w rows at a pitch of 64).
+    MapCuller.keyframes_device(pools) launches without a host round trip,
+    download() synchronises and returns the same per-problem results. A run
+    mutates the pools: upload() restores the inputs."""
 
-    _IO = ("mp", "conn_w", "ordered", "parent", "kf_bad", "Tcp", "ref_kf", "bad")
+    _KF_COLS = ("id", "n", "T", "kps_un", "uright", "mp")
+    _PT_COLS, _PT_OUT = ("ref_kf", "bad"), ("n_obs", "obs")
+    _GRAPH = ("conn_w", "ordered", "parent", "kf_bad", "Tcp")
+    _IO = ("mp",) + _GRAPH + _PT_COLS
 
     def __init__(self, culler, problems, device=0):
-        self.culler, self.device, self.ns = culler, device, len(problems)
-        self.parts = [_sin_map_arrays(p["map"]) for p in problems]
+        super().__init__(problems, "cur", self._KF_COLS, self._PT_COLS)
+        self.culler, K, M, W = culler, self.K, self.M, LM_MAX_MAP_KF
         self.graphs = [_kfc_graph_arrays(p, kfs) for p, (kfs, _, _) in zip(problems, self.parts)]
-        prob, k0, m0 = [], 0, 0
-        for (kfs, M, _), p in zip(self.parts, problems):
-            prob.append([k0, len(kfs), m0, M, int(p["cur"])])
-            k0, m0 = k0 + len(kfs), m0 + M
-        self.prob = np.array(prob or [[0, 0, 0, 0, 0]], np.int32)
-        self.K, self.M = max(1, k0), max(1, m0)
-        self.pitch = P = max([1] + [k["n"] for kfs, _, _ in self.parts for k in kfs])
-        K, M, S, W = self.K, self.M, max(1, self.ns), LM_MAX_MAP_KF
-        h = self.host = dict(
-            id=np.zeros(K, np.int32), n=np.zeros(K, np.int32), T=np.zeros((K, 16), np.float32),
-            kps_un=np.zeros((K, P), KP_DTYPE), uright=np.full((K, P), -1, np.float32),
-            depth=np.full((K, P), -1, np.float32), mp=np.full((K, P), -1, np.int32),
-            conn_w=np.zeros((K, W), np.int32), ordered=np.full((K, W), -1, np.int32),
-            parent=np.full(K, -1, np.int32), not_erase=np.zeros(K, np.uint8), kf_bad=np.zeros(K, np.uint8),
-            Tcp=np.zeros((K, 16), np.float32), ref_kf=np.zeros(M, np.int32), bad=np.ones(M, np.uint8))
-        for (kfs, Mp, pts), g, row in zip(self.parts, self.graphs, prob):
+        h = {c: self.column(c, K, shape, dt) for c, shape, dt in (
+            ("depth", (self.pitch,), np.float32), ("conn_w", (W,), np.int32), ("ordered", (W,), np.int32),
+            ("parent", (), np.int32), ("not_erase", (), np.uint8), ("kf_bad", (), np.uint8),
+            ("Tcp", (16,), np.float32))}
+        for (kfs, _, _), g, (k0, nk, _, _, _) in zip(self.parts, self.graphs, self.prob):
+            h["conn_w"][k0:k0 + nk, :nk] = g["conn_w"]
+            for name in ("ordered", "parent", "not_erase", "kf_bad", "Tcp"):
+                h[name][k0:k0 + nk] = g[name]
             for j, k in enumerate(kfs):
-                x, n = row[0] + j, k["n"]
-                h["id"][x], h["n"][x], h["T"][x] = k["id"], n, k["Tcw"]
-                h["kps_un"][x, :n], h["uright"][x, :n], h["mp"][x, :n] = k["kps_un"], k["uright"], k["mp"]
-                h["depth"][x, :n] = g["depth"][j]
-                h["conn_w"][x, :len(kfs)] = g["conn_w"][j]
-                for name in ("ordered", "parent", "not_erase", "kf_bad", "Tcp"):
-                    h[name][x] = g[name][j]
-            h["ref_kf"][row[2]:row[2] + Mp], h["bad"][row[2]:row[2] + Mp] = pts["ref_kf"], pts["bad"]
-        mk = lambda a: DeviceBuffer.from_array(a, device)
-        b = self.bufs = {k: mk(v) for k, v in h.items()}
-        b.update(prob=mk(self.prob), to_be_erased=DeviceBuffer(K, device), n_obs=DeviceBuffer(M * 4, device),
-                 obs=DeviceBuffer(M * W * 2, device), result=DeviceBuffer(S * C.sizeof(LmKfcResult), device),
-                 err=mk(np.zeros(1, np.int32)))
-        self.batch = LmKfcDeviceBatch(
-            K, P, M, *[b[k].ptr for k in (
+                h["depth"][k0 + j, :k["n"]] = g["depth"][j]
+        if device is not None:
+            b = self.alloc(device, LmKfcResult, to_be_erased=K, n_obs=M * 4, obs=M * W * 2)
+            self.batch = LmKfcDeviceBatch(K, self.pitch, M, *[b[k].ptr for k in (
                 "prob", "id", "n", "T", "kps_un", "uright", "depth", "mp", "conn_w", "ordered", "parent",
-                "not_erase", "kf_bad", "to_be_erased", "Tcp", "ref_kf", "bad", "n_obs", "obs", "result",
-                "err")])
-
-    def upload(self):
-        for name in self._IO:
-            a = self.host[name]
-            check(lib().orbpl_memcpy_htod(self.device, self.bufs[name].ptr, _ptr(a), a.nbytes),
-                  "orbpl_memcpy_htod")
+                "not_erase", "kf_bad", "to_be_erased", "Tcp", "ref_kf", "bad", "n_obs", "obs", "result", "err")])
 
     def run(self, stream=None):
         self.culler.keyframes_device(self, stream)
 
     def download(self):
-        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
-        b, K, M, P, W = self.bufs, self.K, self.M, self.pitch, LM_MAX_MAP_KF
-        if int(b["err"].download(np.int32, 1)[0]):
-            raise OrbplError("orblm_keyframe_culling_batch_device: a problem lies outside the pools")
-        mp = b["mp"].download(np.int32, (K, P))
-        kf = dict(conn_w=b["conn_w"].download(np.int32, (K, W)), ordered=b["ordered"].download(np.int32, (K, W)),
-                  parent=b["parent"].download(np.int32, K), kf_bad=b["kf_bad"].download(np.uint8, K),
-                  to_be_erased=b["to_be_erased"].download(np.uint8, K), Tcp=b["Tcp"].download(np.float32, (K, 16)))
-        pt = dict(ref_kf=b["ref_kf"].download(np.int32, M), bad=b["bad"].download(np.uint8, M),
-                  n_obs=b["n_obs"].download(np.int32, M), obs=b["obs"].download(np.int16, (M, W)))
-        sz = C.sizeof(LmKfcResult)
-        res = b["result"].download(np.uint8, max(1, self.ns) * sz).tobytes()
+        parts = self.fetch("orblm_keyframe_culling_batch_device: a problem lies outside the pools",
+                           self._PT_COLS + self._PT_OUT, self._GRAPH)
+        tbe = self.bufs["to_be_erased"].download(np.uint8, self.K)
         outs = []
-        for s, ((kfs, Mp, pts), row) in enumerate(zip(self.parts, self.prob)):
-            out = {name: v.copy() for name, v in pts.items()}
-            out.update({name: v[row[2]:row[2] + Mp].copy() for name, v in pt.items()})
-            out["mp"] = [mp[row[0] + j, :k["n"]].copy() for j, k in enumerate(kfs)]
-            g = {name: v[row[0]:row[0] + len(kfs)].copy() for name, v in kf.items()}
-            g["conn_w"] = g["conn_w"][:, :len(kfs)].copy()
-            outs.append(_kfc_result_out(out, g, LmKfcResult.from_buffer_copy(res[s * sz:(s + 1) * sz])))
+        for (out, g, r), (k0, nk, _, _, _) in zip(parts, self.prob):
+            g.update(conn_w=g["conn_w"][:, :nk].copy(), to_be_erased=tbe[k0:k0 + nk].copy())
+            outs.append(_kfc_result_out(out, g, r))
         return outs
+
+
+# the functions that set the library's argtypes, in file order: lib() walks them once
+_DECLARE = (_declare_core, _declare_track, _declare_lines, _declare_voc, _declare_reloc, _declare_reloc_device,
+            _declare_localmap, _declare_fuse, _declare_cull)

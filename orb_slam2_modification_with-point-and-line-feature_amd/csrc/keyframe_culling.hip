@@ -29,6 +29,7 @@
 #include "../../include/orbpl.h"
 #include "block_ops.h"
 #include "host_stage.h"
+#include "map_pool.h"
 #include "map_rows.h"
 #include "orbpl_runtime.h"
 #include "track_common.h"
@@ -449,73 +450,22 @@ int check_graph(const orblm_kfc_problem& q) {
 
 int shared_fail() { return arg_fail("a keyframe, point or graph array belongs to two problems"); }
 
-bool any_shared(std::vector<const void*>& owned) {
-  std::sort(owned.begin(), owned.end());
-  return std::adjacent_find(owned.begin(), owned.end()) != owned.end();
+// what both calls write of the map: the slots and bad (in/out), the observation rows (out)
+constexpr uint32_t kCullIo = MapPool::kMp | MapPool::kBad, kCullOut = MapPool::kNObs | MapPool::kObs;
+
+// after the launch: the device's copies of those columns into the pool, then
+// back to the maps with the columns of `more`
+int cull_download(MapPool& H, HostStage& st, uint32_t more, const int32_t* d_mp, const uint8_t* d_bad,
+                  const int32_t* d_n_obs, const int16_t* d_obs) {
+  H.pack(kCullOut);
+  st.back(H.mp, d_mp);
+  st.back(H.bad, d_bad);
+  st.back(H.n_obs, d_n_obs);
+  st.back(H.obs, d_obs);
+  if (st.rc()) return st.rc();
+  H.unpack(kCullIo | kCullOut | more);
+  return ORBPL_OK;
 }
-
-// the keyframe and point pools that both calls stage: the slots, uright, n and
-// the point state the observation rows need
-struct CullPools {
-  std::vector<int32_t> prob, hn, hmp;
-  std::vector<float> hur;
-  std::vector<uint8_t> hbad;
-  int nkf = 0, nmp = 0, pitch = 1;
-
-  void add(const orblm_map& m, int last) {
-    prob.insert(prob.end(), {nkf, m.nkf, nmp, m.M, last});
-    nkf += m.nkf;
-    nmp += m.M;
-    for (int k = 0; k < m.nkf; k++) pitch = std::max(pitch, m.kf[k].n);
-  }
-  // after every add
-  void pack(const std::vector<const orblm_map*>& maps) {
-    const size_t K = (size_t)nkf, P = (size_t)pitch, M = (size_t)std::max(nmp, 1);
-    hn.assign(K, 0);
-    hmp.assign(K * P, -1);
-    hur.assign(K * P, -1.0f);
-    hbad.assign(M, 1);
-    size_t g = 0, q = 0;
-    for (const orblm_map* m : maps) {
-      for (int k = 0; k < m->nkf; k++, g++) {
-        const orblm_map_keyframe& f = m->kf[k];
-        hn[g] = f.n;
-        if (f.n) {
-          memcpy(&hmp[g * P], f.mp, (size_t)f.n * 4);
-          memcpy(&hur[g * P], f.uright, (size_t)f.n * 4);
-        }
-      }
-      if (m->M) memcpy(&hbad[q], m->bad, (size_t)m->M);
-      q += (size_t)m->M;
-    }
-  }
-  // slots, bad, n_obs and obs back to the maps
-  int unpack(HostStage& st, const std::vector<const orblm_map*>& maps, const int32_t* d_mp,
-             const uint8_t* d_bad, const int32_t* d_n_obs, const int16_t* d_obs) {
-    const size_t K = (size_t)nkf, P = (size_t)pitch, M = (size_t)std::max(nmp, 1);
-    std::vector<int32_t> mp(K * P), nobs(M);
-    std::vector<int16_t> obs(M * kMapKF);
-    std::vector<uint8_t> bad(M);
-    st.back(mp, d_mp);
-    st.back(bad, d_bad);
-    st.back(nobs, d_n_obs);
-    st.back(obs, d_obs);
-    if (st.rc()) return st.rc();
-    size_t g = 0, q = 0;
-    for (const orblm_map* m : maps) {
-      for (int k = 0; k < m->nkf; k++, g++)
-        if (m->kf[k].n) memcpy(m->kf[k].mp, &mp[g * P], (size_t)m->kf[k].n * 4);
-      if (m->M) {
-        const size_t n = (size_t)m->M;
-        memcpy(m->bad, &bad[q], n);
-        memcpy(m->n_obs, &nobs[q], n * 4);
-        memcpy(m->obs, &obs[q * kMapKF], n * kMapKF * 2);
-        q += n;
-      }
-    }
-    return ORBPL_OK;
-  }
-};
 
 }  // namespace
 
@@ -539,43 +489,31 @@ int orblm_keyframe_culling(const orbpl_camera* cam, int nlevels, orblm_kfc_probl
   if (nlevels < 1 || nlevels > 16) return arg_fail("nlevels outside [1, 16]");
   if (n < 0 || (n > 0 && !problems)) return arg_fail("bad argument");
   int rc;
-  std::vector<int32_t> stamp;
-  std::vector<uint8_t> ref_seen;
-  std::vector<const void*> owned;
-  std::vector<const orblm_map*> maps;
-  CullPools H;
+  MapPool H;
   for (int p = 0; p < n; p++) {
     const orblm_kfc_problem& q = problems[p];
     const orblm_map& m = q.map;
-    if ((rc = check_map(m, nlevels, stamp, ref_seen))) return rc;
+    if ((rc = check_map(m, nlevels))) return rc;
     if ((rc = check_graph(q))) return rc;
-    if (m.M) owned.push_back(m.bad);
-    for (int k = 0; k < m.nkf; k++)
-      if (m.kf[k].n) owned.push_back(m.kf[k].mp);
-    owned.insert(owned.end(), {q.conn_w, q.ordered, q.parent, q.kf_bad, q.to_be_erased, q.Tcp});
-    maps.push_back(&m);
+    if (m.M) H.owned.push_back(m.bad);
+    H.owned.insert(H.owned.end(), {q.conn_w, q.ordered, q.parent, q.kf_bad, q.to_be_erased, q.Tcp});
     H.add(m, q.cur);
   }
-  if (any_shared(owned)) return shared_fail();
+  if (H.shares_an_array()) return shared_fail();
   if (n == 0) return ORBPL_OK;
-  H.pack(maps);
-  const size_t K = (size_t)H.nkf, P = (size_t)H.pitch, M = (size_t)std::max(H.nmp, 1), N = (size_t)n;
-  std::vector<int32_t> hid(K), hcw(K * kMapKF, 0), hord(K * kMapKF, -1), hpar(K), href(M, 0);
-  std::vector<float> hT(K * 16), hdepth(K * P, -1.0f);
-  std::vector<orbpl_keypoint> hk(K * P);
+  H.pack(MapPool::kId | MapPool::kN | MapPool::kTcw | MapPool::kKpsUn | MapPool::kUright | MapPool::kRefKf |
+         kCullIo);
+  const size_t K = H.K(), P = H.P(), M = H.M(), N = (size_t)n;
+  // the graph columns, at the pool's keyframe offsets
+  std::vector<int32_t> hcw(K * kMapKF, 0), hord(K * kMapKF, -1), hpar(K);
+  std::vector<float> hdepth(K * P, -1.0f);
   std::vector<uint8_t> hne(K), hkb(K);
-  size_t g = 0, pt = 0;
   for (int p = 0; p < n; p++) {
     const orblm_kfc_problem& q = problems[p];
     const orblm_map& m = q.map;
+    size_t g = H.kf0(p);
     for (int k = 0; k < m.nkf; k++, g++) {
-      const orblm_map_keyframe& f = m.kf[k];
-      hid[g] = f.id;
-      memcpy(&hT[g * 16], f.Tcw, 64);
-      if (f.n) {
-        memcpy(&hk[g * P], f.kps_un, (size_t)f.n * sizeof(orbpl_keypoint));
-        memcpy(&hdepth[g * P], q.depth[k], (size_t)f.n * 4);
-      }
+      if (m.kf[k].n) memcpy(&hdepth[g * P], q.depth[k], (size_t)m.kf[k].n * 4);
       memcpy(&hcw[g * kMapKF], q.conn_w + (size_t)k * m.nkf, (size_t)m.nkf * 4);
       for (int x = 0; x < kMapKF && q.ordered[k * kMapKF + x] >= 0; x++)
         hord[g * kMapKF + x] = q.ordered[k * kMapKF + x];
@@ -583,8 +521,6 @@ int orblm_keyframe_culling(const orbpl_camera* cam, int nlevels, orblm_kfc_probl
       hne[g] = q.not_erase[k];
       hkb[g] = q.kf_bad[k];
     }
-    if (m.M) memcpy(&href[pt], m.ref_kf, (size_t)m.M * 4);
-    pt += (size_t)m.M;
   }
   HostStage st;
   orblm_kfc_device_batch b{};
@@ -592,13 +528,13 @@ int orblm_keyframe_culling(const orbpl_camera* cam, int nlevels, orblm_kfc_probl
   b.kp_pitch = H.pitch;
   b.nmp = H.nmp;
   b.d_prob = st.in(H.prob);
-  b.d_kf_id = st.in(hid);
-  b.d_kf_n = st.in(H.hn);
-  b.d_kf_Tcw = st.in(hT);
-  b.d_kps_un = st.in(hk);
-  b.d_uright = st.in(H.hur);
+  b.d_kf_id = st.in(H.id);
+  b.d_kf_n = st.in(H.n);
+  b.d_kf_Tcw = st.in(H.Tcw);
+  b.d_kps_un = st.in(H.kps_un);
+  b.d_uright = st.in(H.uright);
   b.d_depth = st.in(hdepth);
-  b.d_mp = st.in(H.hmp);
+  b.d_mp = st.in(H.mp);
   b.d_conn_w = st.in(hcw);
   b.d_ordered = st.in(hord);
   b.d_parent = st.in(hpar);
@@ -606,8 +542,8 @@ int orblm_keyframe_culling(const orbpl_camera* cam, int nlevels, orblm_kfc_probl
   b.d_kf_bad = st.in(hkb);
   b.d_to_be_erased = st.zeros<uint8_t>(K);
   b.d_Tcp = st.zeros<float>(K * 16);
-  b.d_ref_kf = st.in(href);
-  b.d_bad = st.in(H.hbad);
+  b.d_ref_kf = st.in(H.ref_kf);
+  b.d_bad = st.in(H.bad);
   b.d_n_obs = st.out<int32_t>(M);
   b.d_obs = st.out<int16_t>(M * kMapKF);
   b.d_result = st.out<orblm_kfc_result>(N);
@@ -625,14 +561,13 @@ int orblm_keyframe_culling(const orbpl_camera* cam, int nlevels, orblm_kfc_probl
   st.back(hkb, b.d_kf_bad);
   st.back(htbe, b.d_to_be_erased);
   st.back(hTcp, b.d_Tcp);
-  st.back(href, b.d_ref_kf);
-  if ((rc = H.unpack(st, maps, b.d_mp, b.d_bad, b.d_n_obs, b.d_obs))) return rc;
-  g = 0;
-  pt = 0;
+  st.back(H.ref_kf, b.d_ref_kf);
+  if ((rc = cull_download(H, st, MapPool::kRefKf, b.d_mp, b.d_bad, b.d_n_obs, b.d_obs))) return rc;
   for (int p = 0; p < n; p++) {
     orblm_kfc_problem& q = problems[p];
     const orblm_map& m = q.map;
-    const size_t g0 = g;
+    const size_t g0 = H.kf0(p);
+    size_t g = g0;
     for (int k = 0; k < m.nkf; k++, g++) {
       memcpy(q.conn_w + (size_t)k * m.nkf, &hcw[g * kMapKF], (size_t)m.nkf * 4);
       memcpy(q.ordered + (size_t)k * kMapKF, &hord[g * kMapKF], kMapKF * 4);
@@ -646,8 +581,6 @@ int orblm_keyframe_culling(const orbpl_camera* cam, int nlevels, orblm_kfc_probl
         const int k = q.result.list[e];
         memcpy(q.Tcp + (size_t)k * 16, &hTcp[(g0 + k) * 16], 64);
       }
-    if (m.M) memcpy(m.ref_kf, &href[pt], (size_t)m.M * 4);
-    pt += (size_t)m.M;
   }
   return ORBPL_OK;
 }
@@ -656,16 +589,14 @@ int orblm_cull_recent(int nlevels, orblm_recent_problem* problems, int n) {
   if (nlevels < 1 || nlevels > 16) return arg_fail("nlevels outside [1, 16]");
   if (n < 0 || (n > 0 && !problems)) return arg_fail("bad argument");
   int rc;
-  std::vector<int32_t> stamp, ext;
-  std::vector<uint8_t> ref_seen, seen;
-  std::vector<const void*> owned;
-  std::vector<const orblm_map*> maps;
-  CullPools H;
+  std::vector<int32_t> ext;
+  std::vector<uint8_t> seen;
+  MapPool H;
   int nrec = 0, nlines = 0, nrl = 0, lpitch = 1;
   for (int p = 0; p < n; p++) {
     const orblm_recent_problem& q = problems[p];
     const orblm_map& m = q.map;
-    if ((rc = check_map(m, nlevels, stamp, ref_seen))) return rc;
+    if ((rc = check_map(m, nlevels))) return rc;
     if (q.n_recent < 0 || q.n_recent_lines < 0) return arg_fail("negative list length");
     if (q.L < 0 || q.L > kKcMaxLines) return arg_fail("map lines outside [0, 64 * 256]");
     if ((m.M > 0 && !q.first_kf) || (q.n_recent > 0 && (!q.recent || !q.reason)) ||
@@ -692,40 +623,32 @@ int orblm_cull_recent(int nlevels, orblm_recent_problem* problems, int n) {
       if (q.nl[k] > 0 && !q.ml[k]) return arg_fail("NULL culling arrays");
       for (int j = 0; j < q.nl[k]; j++)
         if (q.ml[k][j] < -1 || q.ml[k][j] >= q.L) return arg_fail("line slot outside [-1, L)");
-      if (q.nl[k]) owned.push_back(q.ml[k]);
-      if (m.kf[k].n) owned.push_back(m.kf[k].mp);
+      if (q.nl[k]) H.owned.push_back(q.ml[k]);
       lpitch = std::max(lpitch, q.nl[k]);
     }
-    if (m.M) owned.push_back(m.bad);
-    if (q.L) owned.push_back(q.line_bad);
-    if (q.n_recent) owned.insert(owned.end(), {q.recent, q.reason});
-    if (q.n_recent_lines) owned.insert(owned.end(), {q.recent_lines, q.line_reason});
+    if (m.M) H.owned.push_back(m.bad);
+    if (q.L) H.owned.push_back(q.line_bad);
+    if (q.n_recent) H.owned.insert(H.owned.end(), {q.recent, q.reason});
+    if (q.n_recent_lines) H.owned.insert(H.owned.end(), {q.recent_lines, q.line_reason});
     ext.insert(ext.end(), {nrec, q.n_recent, nlines, q.L, nrl, q.n_recent_lines});
     nrec += q.n_recent;
     nlines += q.L;
     nrl += q.n_recent_lines;
-    maps.push_back(&m);
     H.add(m, q.cur_id);
   }
-  if (any_shared(owned)) return shared_fail();
+  if (H.shares_an_array()) return shared_fail();
   if (n == 0) return ORBPL_OK;
-  H.pack(maps);
-  const size_t K = (size_t)H.nkf, M = (size_t)std::max(H.nmp, 1), LP = (size_t)lpitch,
-               NL = (size_t)std::max(nlines, 1), N = (size_t)n;
-  std::vector<int32_t> hvis(M, 0), hfound(M, 0), hfirst(M, 0), hrec((size_t)std::max(nrec, 1)),
-      hnl(K), hml(K * LP, -1), hlvis(NL, 0), hlfound(NL, 0), hlfirst(NL, 0), hlnobs(NL, 0),
-      hrl((size_t)std::max(nrl, 1));
+  H.pack(MapPool::kN | MapPool::kUright | MapPool::kNVisible | MapPool::kNFound | kCullIo);
+  const size_t K = H.K(), M = H.M(), LP = (size_t)lpitch, NL = (size_t)std::max(nlines, 1), N = (size_t)n;
+  std::vector<int32_t> hfirst(M, 0), hrec((size_t)std::max(nrec, 1)), hnl(K), hml(K * LP, -1), hlvis(NL, 0),
+      hlfound(NL, 0), hlfirst(NL, 0), hlnobs(NL, 0), hrl((size_t)std::max(nrl, 1));
   std::vector<uint8_t> hlbad(NL, 1), hkb(K, 0);
-  size_t g = 0;
   for (int p = 0; p < n; p++) {
     const orblm_recent_problem& q = problems[p];
     const orblm_map& m = q.map;
-    const size_t m0 = (size_t)H.prob[5 * p + 2], l0 = (size_t)ext[6 * p + 2];
-    if (m.M) {
-      memcpy(&hvis[m0], m.n_visible, (size_t)m.M * 4);
-      memcpy(&hfound[m0], m.n_found, (size_t)m.M * 4);
-      memcpy(&hfirst[m0], q.first_kf, (size_t)m.M * 4);
-    }
+    const size_t l0 = (size_t)ext[6 * p + 2];
+    size_t g = H.kf0(p);
+    if (m.M) memcpy(&hfirst[H.mp0(p)], q.first_kf, (size_t)m.M * 4);
     if (q.n_recent) memcpy(&hrec[(size_t)ext[6 * p]], q.recent, (size_t)q.n_recent * 4);
     if (q.n_recent_lines) memcpy(&hrl[(size_t)ext[6 * p + 4]], q.recent_lines, (size_t)q.n_recent_lines * 4);
     if (q.L) {
@@ -750,13 +673,13 @@ int orblm_cull_recent(int nlevels, orblm_recent_problem* problems, int n) {
   a.line_pitch = lpitch;
   a.d_prob = st.in(H.prob);
   a.d_ext = st.in(ext);
-  a.d_kf_n = st.in(H.hn);
+  a.d_kf_n = st.in(H.n);
   a.d_kf_bad = st.in(hkb);
-  a.d_uright = st.in(H.hur);
-  a.d_mp = st.in(H.hmp);
-  a.d_bad = st.in(H.hbad);
-  a.d_n_visible = st.in(hvis);
-  a.d_n_found = st.in(hfound);
+  a.d_uright = st.in(H.uright);
+  a.d_mp = st.in(H.mp);
+  a.d_bad = st.in(H.bad);
+  a.d_n_visible = st.in(H.n_visible);
+  a.d_n_found = st.in(H.n_found);
   a.d_first_kf = st.in(hfirst);
   a.d_n_obs = st.out<int32_t>(M);
   a.d_obs = st.out<int16_t>(M * kMapKF);
@@ -787,10 +710,10 @@ int orblm_cull_recent(int nlevels, orblm_recent_problem* problems, int n) {
   st.back(onout, a.d_n_out);
   st.back(hml, a.d_ml);
   st.back(hlbad, a.d_line_bad);
-  if ((rc = H.unpack(st, maps, a.d_mp, a.d_bad, a.d_n_obs, a.d_obs))) return rc;
-  g = 0;
+  if ((rc = cull_download(H, st, 0, a.d_mp, a.d_bad, a.d_n_obs, a.d_obs))) return rc;
   for (int p = 0; p < n; p++) {
     orblm_recent_problem& q = problems[p];
+    size_t g = H.kf0(p);
     const size_t r0 = (size_t)ext[6 * p], l0 = (size_t)ext[6 * p + 2], rl0 = (size_t)ext[6 * p + 4];
     if (q.n_recent) memcpy(q.reason, &oreason[r0], (size_t)q.n_recent * 4);
     if (q.n_recent_lines) memcpy(q.line_reason, &olreason[rl0], (size_t)q.n_recent_lines * 4);

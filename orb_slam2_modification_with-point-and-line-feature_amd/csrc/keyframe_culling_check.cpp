@@ -5,55 +5,17 @@
 // fails after the pools were packed. With a device present the refusals are
 // still checked. The library's reporters are replaced by stand-ins: they are
 // not what is under test.
-#include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "keyframe_culling.hip"
-
-namespace {
-std::string g_msg;
-}
-
-int orbpl::hip_fail(hipError_t e, const char* what, int line) {
-  g_msg = std::string(what) + ": " + hipGetErrorString(e);
-  (void)line;
-  return ORBPL_ERR_HIP;
-}
-int orbpl::arg_fail(const char* msg) {
-  g_msg = msg;
-  return ORBPL_ERR_ARG;
-}
-
-#define EXPECT(cond)                                                          \
-  do {                                                                        \
-    if (!(cond)) {                                                            \
-      printf("FAILED line %d: %s (last: %s)\n", __LINE__, #cond, g_msg.c_str()); \
-      return 1;                                                               \
-    }                                                                         \
-  } while (0)
+#include "check_common.h"
 
 namespace {
 
-// three keyframes (ids 0, 5, 9) of three features, two points: point 0 in all
-// three, point 1 in the second; keyframe 2 is the current one, its list [1, 0]
-struct TinyMap {
-  float T[3][16] = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1},
-                    {1, 0, 0, -0.2f, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1},
-                    {1, 0, 0, -0.4f, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
-  orbpl_keypoint kp[3][3] = {};
-  float ur[3][3] = {{300, -1, 100}, {290, 50, -1}, {280, -1, -1}};
-  uint8_t kdesc[3][3 * 32] = {};
-  int32_t mp[3][3] = {{0, -1, -1}, {0, 1, -1}, {0, -1, -1}};
-  orblm_map_keyframe kf[3];
-  float xyz[6] = {0, 0, 4, 0.5f, 0, 5}, normal[6] = {0, 0, 1, 0, 0, 1};
-  float mind[2] = {1, 1}, maxd[2] = {10, 10};
-  uint8_t desc[64] = {}, bad[2] = {0, 0};
-  int32_t ref[2] = {0, 1}, vis[2] = {3, 4}, found[2] = {2, 2}, rep[2], nobs[2], src[4];
-  int16_t obs[128];
-  orblm_map m;
-  // the graph
+// the map of three keyframes with its graph (keyframe 2 is the current one, its
+// list [1, 0]), the recent lists and the line table
+struct CullMap : TinyMap {
   float depth[3][3] = {{1, 1, 1}, {1, 1, 1}, {1, 1, 1}};
   const float* dptr[3] = {depth[0], depth[1], depth[2]};
   int32_t cw[9] = {0, 1, 1, 1, 0, 1, 1, 1, 0};
@@ -69,12 +31,7 @@ struct TinyMap {
   int32_t lvis[2] = {3, 3}, lfound[2] = {2, 2}, lfirst[2] = {-1, 9}, lnobs[2] = {2, 5};
   int32_t rlines[2] = {0, 1}, lreason[2] = {-1, -1};
 
-  TinyMap() {
-    for (int k = 0; k < 3; k++) {
-      for (int i = 0; i < 3; i++) kp[k][i].x = 320.f + 10 * i, kp[k][i].y = 240.f;
-      kf[k] = {k == 0 ? 0 : 4 * k + 1, T[k], 3, kp[k], ur[k], kdesc[k], mp[k], nullptr};
-    }
-    m = {3, kf, 2, xyz, normal, mind, maxd, desc, ref, bad, vis, found, rep, nobs, obs, src};
+  CullMap() {
     for (int i = 0; i < 3 * 64; i++) ord[i] = -1;
     ord[0] = 1, ord[1] = 2, ord[64] = 0, ord[65] = 2, ord[128] = 1, ord[129] = 0;
   }
@@ -122,7 +79,7 @@ const orbpl_camera kCam = {517.f, 516.f, 318.f, 255.f, 0, 0, 0, 0, 0, 40.f, 3.f,
 int main() {
 #define KFC_REFUSED(edit, text)                                        \
   do {                                                                 \
-    TinyMap t;                                                         \
+    CullMap t;                                                         \
     orblm_kfc_problem p = t.kfc();                                     \
     edit;                                                              \
     EXPECT(orblm_keyframe_culling(&kCam, 8, &p, 1) == ORBPL_ERR_ARG);  \
@@ -153,7 +110,7 @@ int main() {
   KFC_REFUSED(t.parent[2] = -2, "parent outside the table or naming its own keyframe");
   KFC_REFUSED(t.parent[1] = -1, "good keyframe with id != 0 and no parent");
   {
-    TinyMap t;
+    CullMap t;
     orblm_kfc_problem two[2] = {t.kfc(), t.kfc()};
     EXPECT(orblm_keyframe_culling(&kCam, 8, two, 2) == ORBPL_ERR_ARG);
     EXPECT(g_msg == "a keyframe, point or graph array belongs to two problems");
@@ -167,7 +124,7 @@ int main() {
   }
 #define RC_REFUSED(edit, text)                               \
   do {                                                       \
-    TinyMap t;                                               \
+    CullMap t;                                               \
     orblm_recent_problem p = t.rc();                         \
     edit;                                                    \
     EXPECT(orblm_cull_recent(8, &p, 1) == ORBPL_ERR_ARG);    \
@@ -188,7 +145,7 @@ int main() {
   RC_REFUSED(p.reason = nullptr, "NULL culling arrays");
   RC_REFUSED(p.n_recent = -1, "negative list length");
   {
-    TinyMap t;
+    CullMap t;
     orblm_recent_problem two[2] = {t.rc(), t.rc()};
     EXPECT(orblm_cull_recent(8, two, 2) == ORBPL_ERR_ARG);
     EXPECT(g_msg == "a keyframe, point or graph array belongs to two problems");
@@ -200,8 +157,8 @@ int main() {
     return 0;
   }
   {
-    TinyMap t;
-    const TinyMap before;
+    CullMap t;
+    const CullMap before;
     orblm_kfc_problem p = t.kfc();
     EXPECT(orblm_keyframe_culling(&kCam, 8, &p, 1) == ORBPL_ERR_HIP);
     EXPECT(!memcmp(t.mp, before.mp, sizeof(t.mp)) && !memcmp(t.cw, before.cw, sizeof(t.cw)));

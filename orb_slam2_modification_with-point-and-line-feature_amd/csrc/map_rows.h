@@ -98,9 +98,8 @@ __device__ __forceinline__ void rank_by_id(const int* id, int nkf, int* by_id, i
   }
 }
 
-// the refusals of one map (before any device call); stamp, ref_seen: scratch
-inline int check_map(const orblm_map& m, int nlevels, std::vector<int32_t>& stamp,
-                     std::vector<uint8_t>& ref_seen) {
+// the refusals of one map (before any device call)
+inline int check_map(const orblm_map& m, int nlevels) {
   if (m.nkf < 1 || m.nkf > kMapKF) return arg_fail("map with no keyframe or more than 64");
   if (!m.kf) return arg_fail("NULL keyframe table");
   if (m.M < 0 || m.M > kMapMaxPoints) return arg_fail("map points outside [0, 64 * 2048]");
@@ -108,8 +107,8 @@ inline int check_map(const orblm_map& m, int nlevels, std::vector<int32_t>& stam
                   !m.bad || !m.n_visible || !m.n_found || !m.replaced_by || !m.n_obs || !m.obs ||
                   !m.desc_src))
     return arg_fail("NULL map point arrays");
-  stamp.assign((size_t)m.M, -1);
-  ref_seen.assign((size_t)m.M, 0);
+  std::vector<int32_t> stamp((size_t)m.M, -1);   // the last keyframe a point was met in
+  std::vector<uint8_t> ref_seen((size_t)m.M, 0);
   for (int k = 0; k < m.nkf; k++) {
     const orblm_map_keyframe& f = m.kf[k];
     if (!f.Tcw) return arg_fail("NULL keyframe pose");

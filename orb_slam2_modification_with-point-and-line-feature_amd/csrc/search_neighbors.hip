@@ -46,6 +46,7 @@
 #include "block_ops.h"
 #include "host_stage.h"
 #include "lsd_math.h"
+#include "map_pool.h"
 #include "map_rows.h"
 #include "match_common.h"
 #include "orbpl_runtime.h"
@@ -653,85 +654,40 @@ using namespace orbpl;
 
 namespace {
 
-// The pools of a host call: every map of the call, flattened.
-struct SnHostPool {
-  std::vector<const orblm_map*> maps;
-  std::vector<int32_t> prob;
-  int nkf = 0, nmp = 0, pitch = 1, list_pitch = 1;
+// The staged pools of a host call: the pool's packed columns on the device.
+struct SnStaged {
+  MapPool H;
   HostStage st;
   orblm_sin_device_batch b{};
 
-  void add(const orblm_map* m, int cur) {
-    maps.push_back(m);
-    prob.insert(prob.end(), {nkf, m->nkf, nmp, m->M, cur});
-    nkf += m->nkf;
-    nmp += m->M;
-    for (int k = 0; k < m->nkf; k++) pitch = std::max(pitch, m->kf[k].n);
-    list_pitch = std::max(list_pitch, m->M);
-  }
-
+  // after every H.add; extra_list: a list of the caller's that d_list has to hold
   int upload(int extra_list) {
-    list_pitch = std::max(std::max(list_pitch, pitch), extra_list);
-    const size_t K = (size_t)nkf, P = (size_t)pitch, M = (size_t)std::max(nmp, 1), N = maps.size();
-    std::vector<int32_t> hid(K), hn(K), hmp(K * P, -1), hord(K * kSnKF, -1), href(M, 0), hvis(M, 0),
-        hfound(M, 0);
-    std::vector<float> hT(K * 16), hur(K * P, -1.0f), hxyz(M * 3, 0.f), hnrm(M * 3, 0.f), hmin(M, 0.f),
-        hmax(M, 0.f);
-    std::vector<orbpl_keypoint> hk(K * P);
-    std::vector<uint8_t> hdesc(K * P * 32), hmd(M * 32, 0), hbad(M, 1);
-    size_t g = 0, q = 0;
-    for (const orblm_map* m : maps) {
-      for (int k = 0; k < m->nkf; k++, g++) {
-        const orblm_map_keyframe& f = m->kf[k];
-        hid[g] = f.id;
-        hn[g] = f.n;
-        memcpy(&hT[g * 16], f.Tcw, 64);
-        if (f.n) {
-          memcpy(&hk[g * P], f.kps_un, (size_t)f.n * sizeof(orbpl_keypoint));
-          memcpy(&hur[g * P], f.uright, (size_t)f.n * 4);
-          memcpy(&hdesc[g * P * 32], f.desc, (size_t)f.n * 32);
-          memcpy(&hmp[g * P], f.mp, (size_t)f.n * 4);
-        }
-        if (f.ordered)
-          for (int x = 0; x < kSnKF && f.ordered[x] >= 0; x++) hord[g * kSnKF + x] = f.ordered[x];
-      }
-      if (m->M) {
-        const size_t n = (size_t)m->M;
-        memcpy(&hxyz[q * 3], m->xyz, n * 12);
-        memcpy(&hnrm[q * 3], m->normal, n * 12);
-        memcpy(&hmin[q], m->min_dist, n * 4);
-        memcpy(&hmax[q], m->max_dist, n * 4);
-        memcpy(&hmd[q * 32], m->desc, n * 32);
-        memcpy(&href[q], m->ref_kf, n * 4);
-        memcpy(&hbad[q], m->bad, n);
-        memcpy(&hvis[q], m->n_visible, n * 4);
-        memcpy(&hfound[q], m->n_found, n * 4);
-        q += n;
-      }
-    }
-    const size_t L = (size_t)list_pitch;
-    b.nkf = nkf;
-    b.kp_pitch = pitch;
-    b.nmp = nmp;
+    H.pack(MapPool::kIn);
+    int list_pitch = std::max(H.pitch, extra_list);
+    for (const orblm_map* m : H.maps) list_pitch = std::max(list_pitch, m->M);
+    const size_t M = H.M(), N = H.maps.size(), L = (size_t)list_pitch;
+    b.nkf = H.nkf;
+    b.kp_pitch = H.pitch;
+    b.nmp = H.nmp;
     b.list_pitch = list_pitch;
-    b.d_prob = st.in(prob);
-    b.d_kf_id = st.in(hid);
-    b.d_kf_n = st.in(hn);
-    b.d_kf_Tcw = st.in(hT);
-    b.d_kps_un = st.in(hk);
-    b.d_uright = st.in(hur);
-    b.d_desc = st.in(hdesc);
-    b.d_mp = st.in(hmp);
-    b.d_ordered = st.in(hord);
-    b.d_xyz = st.in(hxyz);
-    b.d_normal = st.in(hnrm);
-    b.d_min_dist = st.in(hmin);
-    b.d_max_dist = st.in(hmax);
-    b.d_mp_desc = st.in(hmd);
-    b.d_ref_kf = st.in(href);
-    b.d_bad = st.in(hbad);
-    b.d_n_visible = st.in(hvis);
-    b.d_n_found = st.in(hfound);
+    b.d_prob = st.in(H.prob);
+    b.d_kf_id = st.in(H.id);
+    b.d_kf_n = st.in(H.n);
+    b.d_kf_Tcw = st.in(H.Tcw);
+    b.d_kps_un = st.in(H.kps_un);
+    b.d_uright = st.in(H.uright);
+    b.d_desc = st.in(H.kf_desc);
+    b.d_mp = st.in(H.mp);
+    b.d_ordered = st.in(H.ordered);
+    b.d_xyz = st.in(H.xyz);
+    b.d_normal = st.in(H.normal);
+    b.d_min_dist = st.in(H.min_dist);
+    b.d_max_dist = st.in(H.max_dist);
+    b.d_mp_desc = st.in(H.desc);
+    b.d_ref_kf = st.in(H.ref_kf);
+    b.d_bad = st.in(H.bad);
+    b.d_n_visible = st.in(H.n_visible);
+    b.d_n_found = st.in(H.n_found);
     b.d_replaced_by = st.out<int32_t>(M);
     b.d_n_obs = st.out<int32_t>(M);
     b.d_obs = st.out<int16_t>(M * kSnKF);
@@ -746,45 +702,22 @@ struct SnHostPool {
 
   // the maps' in/out and out arrays back to the caller; err: the device flag
   int download(int* err) {
-    const size_t K = (size_t)nkf, P = (size_t)pitch, M = (size_t)std::max(nmp, 1);
-    std::vector<int32_t> hmp(K * P), href(M), hvis(M), hfound(M), hrep(M), hnobs(M), hsrc(M * 2);
-    std::vector<int16_t> hobs(M * kSnKF);
-    std::vector<float> hnrm(M * 3), hmin(M), hmax(M);
-    std::vector<uint8_t> hmd(M * 32), hbad(M);
-    st.back(hmp, b.d_mp);
-    st.back(hnrm, b.d_normal);
-    st.back(hmin, b.d_min_dist);
-    st.back(hmax, b.d_max_dist);
-    st.back(hmd, b.d_mp_desc);
-    st.back(hbad, b.d_bad);
-    st.back(hvis, b.d_n_visible);
-    st.back(hfound, b.d_n_found);
-    st.back(hrep, b.d_replaced_by);
-    st.back(hnobs, b.d_n_obs);
-    st.back(hobs, b.d_obs);
-    st.back(hsrc, b.d_desc_src);
+    H.pack(MapPool::kOut);
+    st.back(H.mp, b.d_mp);
+    st.back(H.normal, b.d_normal);
+    st.back(H.min_dist, b.d_min_dist);
+    st.back(H.max_dist, b.d_max_dist);
+    st.back(H.desc, b.d_mp_desc);
+    st.back(H.bad, b.d_bad);
+    st.back(H.n_visible, b.d_n_visible);
+    st.back(H.n_found, b.d_n_found);
+    st.back(H.replaced_by, b.d_replaced_by);
+    st.back(H.n_obs, b.d_n_obs);
+    st.back(H.obs, b.d_obs);
+    st.back(H.desc_src, b.d_desc_src);
     st.back(err, b.d_err, 1);
     if (st.rc()) return st.rc();
-    size_t g = 0, q = 0;
-    for (const orblm_map* m : maps) {
-      for (int k = 0; k < m->nkf; k++, g++)
-        if (m->kf[k].n) memcpy(m->kf[k].mp, &hmp[g * P], (size_t)m->kf[k].n * 4);
-      if (m->M) {
-        const size_t n = (size_t)m->M;
-        memcpy(m->normal, &hnrm[q * 3], n * 12);
-        memcpy(m->min_dist, &hmin[q], n * 4);
-        memcpy(m->max_dist, &hmax[q], n * 4);
-        memcpy(m->desc, &hmd[q * 32], n * 32);
-        memcpy(m->bad, &hbad[q], n);
-        memcpy(m->n_visible, &hvis[q], n * 4);
-        memcpy(m->n_found, &hfound[q], n * 4);
-        memcpy(m->replaced_by, &hrep[q], n * 4);
-        memcpy(m->n_obs, &hnobs[q], n * 4);
-        memcpy(m->obs, &hobs[q * kSnKF], n * kSnKF * 2);
-        memcpy(m->desc_src, &hsrc[q * 2], n * 8);
-        q += n;
-      }
-    }
+    H.unpack((MapPool::kIn | MapPool::kOut) & ~(MapPool::kXyz | MapPool::kRefKf));   // what the call writes
     return ORBPL_OK;
   }
 };
@@ -798,33 +731,13 @@ void launch(const SnArgs& a, int n, hipStream_t s) {
   hipLaunchKernelGGL(k_search_in_neighbors, dim3(n), dim3(kSnThreads), 0, s, a);
 }
 
-}  // namespace
-
-extern "C" {
-
-int orblm_search_in_neighbors_batch_device(const orbpl_camera* cam, const float* scale_factors,
-                                           const float* level_sigma2, int nlevels,
-                                           const orblm_sin_device_batch* b, int n, void* stream) {
+// the device-pool entry; phases: with in-kernel time stamps into d_ticks
+int sn_device(const orbpl_camera* cam, const float* scale_factors, const float* level_sigma2, int nlevels,
+              const orblm_sin_device_batch* b, int n, void* stream, bool phases, long long* d_ticks) {
   SnArgs a{};
   int rc = make_sn_args(cam, scale_factors, level_sigma2, nlevels, &a);
   if (rc) return rc;
-  if (n < 0) return arg_fail("bad argument");
-  if ((rc = check_sn_batch(b))) return rc;
-  if (n == 0) return ORBPL_OK;
-  a.b = *b;
-  launch(a, n, static_cast<hipStream_t>(stream));
-  HIP_CHECK(hipGetLastError());
-  return ORBPL_OK;
-}
-
-int orblm_debug_search_in_neighbors_phases(const orbpl_camera* cam, const float* scale_factors,
-                                           const float* level_sigma2, int nlevels,
-                                           const orblm_sin_device_batch* b, int n, void* stream,
-                                           long long* d_ticks) {
-  SnArgs a{};
-  int rc = make_sn_args(cam, scale_factors, level_sigma2, nlevels, &a);
-  if (rc) return rc;
-  if (n < 0 || !d_ticks) return arg_fail("bad argument");
+  if (n < 0 || (phases && !d_ticks)) return arg_fail("bad argument");
   if ((rc = check_sn_batch(b))) return rc;
   if (n == 0) return ORBPL_OK;
   a.b = *b;
@@ -834,6 +747,23 @@ int orblm_debug_search_in_neighbors_phases(const orbpl_camera* cam, const float*
   return ORBPL_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int orblm_search_in_neighbors_batch_device(const orbpl_camera* cam, const float* scale_factors,
+                                           const float* level_sigma2, int nlevels,
+                                           const orblm_sin_device_batch* b, int n, void* stream) {
+  return sn_device(cam, scale_factors, level_sigma2, nlevels, b, n, stream, false, nullptr);
+}
+
+int orblm_debug_search_in_neighbors_phases(const orbpl_camera* cam, const float* scale_factors,
+                                           const float* level_sigma2, int nlevels,
+                                           const orblm_sin_device_batch* b, int n, void* stream,
+                                           long long* d_ticks) {
+  return sn_device(cam, scale_factors, level_sigma2, nlevels, b, n, stream, true, d_ticks);
+}
+
 int orblm_search_in_neighbors(const orbpl_camera* cam, const float* scale_factors,
                               const float* level_sigma2, int nlevels, orblm_sin_problem* problems,
                               int n) {
@@ -841,32 +771,25 @@ int orblm_search_in_neighbors(const orbpl_camera* cam, const float* scale_factor
   int rc = make_sn_args(cam, scale_factors, level_sigma2, nlevels, &a);
   if (rc) return rc;
   if (n < 0 || (n > 0 && !problems)) return arg_fail("bad argument");
-  SnHostPool H;
-  std::vector<int32_t> stamp;
-  std::vector<uint8_t> ref_seen;
-  std::vector<const void*> owned;
+  SnStaged S;
   for (int p = 0; p < n; p++) {
     const orblm_map& m = problems[p].map;
-    if ((rc = check_map(m, nlevels, stamp, ref_seen))) return rc;
+    if ((rc = check_map(m, nlevels))) return rc;
     if (problems[p].cur < 0 || problems[p].cur >= m.nkf)
       return arg_fail("current keyframe outside the table");
-    if (m.M) owned.push_back(m.xyz);
-    for (int k = 0; k < m.nkf; k++)
-      if (m.kf[k].n) owned.push_back(m.kf[k].mp);
-    H.add(&m, problems[p].cur);
+    if (m.M) S.H.owned.push_back(m.xyz);
+    S.H.add(m, problems[p].cur);
   }
-  std::sort(owned.begin(), owned.end());
-  if (std::adjacent_find(owned.begin(), owned.end()) != owned.end())
-    return arg_fail("a keyframe or point array belongs to two problems");
+  if (S.H.shares_an_array()) return arg_fail("a keyframe or point array belongs to two problems");
   if (n == 0) return ORBPL_OK;
-  if ((rc = H.upload(0))) return rc;
-  a.b = H.b;
+  if ((rc = S.upload(0))) return rc;
+  a.b = S.b;
   launch(a, n, nullptr);   // host-pointer APIs use the null stream
-  H.st.launched();
+  S.st.launched();
   std::vector<orblm_sin_result> hres((size_t)n);
-  H.st.back(hres, H.b.d_result);
+  S.st.back(hres, S.b.d_result);
   int err = 0;
-  if ((rc = H.download(&err))) return rc;
+  if ((rc = S.download(&err))) return rc;
   for (int p = 0; p < n; p++) problems[p].result = hres[p];
   return err ? overflow_fail() : ORBPL_OK;
 }
@@ -879,33 +802,31 @@ int orbm_fuse(const orbpl_camera* cam, const float* scale_factors, const float* 
   if (rc) return rc;
   if (!map || !n_fused || n_list < 0) return arg_fail("bad argument");
   if (n_list > 0 && (!list || !best_idx || !best_dist || !reason)) return arg_fail("NULL list arrays");
-  std::vector<int32_t> stamp;
-  std::vector<uint8_t> ref_seen;
-  if ((rc = check_map(*map, nlevels, stamp, ref_seen))) return rc;
+  if ((rc = check_map(*map, nlevels))) return rc;
   if (kf < 0 || kf >= map->nkf) return arg_fail("keyframe outside the table");
   for (int i = 0; i < n_list; i++)
     if (list[i] < -1 || list[i] >= map->M) return arg_fail("list entry outside [-1, M)");
-  SnHostPool H;
-  H.add(map, kf);
-  if ((rc = H.upload(n_list))) return rc;
-  const size_t L = (size_t)H.list_pitch;
-  a.b = H.b;
+  SnStaged S;
+  S.H.add(*map, kf);
+  if ((rc = S.upload(n_list))) return rc;
+  const size_t L = (size_t)S.b.list_pitch;
+  a.b = S.b;
   a.fuse_only = 1;
   a.fuse_kf = kf;
   a.fuse_n = n_list;
   a.th = th;
-  a.d_fuse_out = H.st.out<int32_t>(3 * L);
-  if (H.st.rc()) return H.st.rc();
-  if (n_list) HIP_CHECK(hipMemcpy(H.b.d_list, list, (size_t)n_list * 4, hipMemcpyHostToDevice));
+  a.d_fuse_out = S.st.out<int32_t>(3 * L);
+  if (S.st.rc()) return S.st.rc();
+  if (n_list) HIP_CHECK(hipMemcpy(S.b.d_list, list, (size_t)n_list * 4, hipMemcpyHostToDevice));
   launch(a, 1, nullptr);
-  H.st.launched();
+  S.st.launched();
   orblm_sin_result res;
-  H.st.back(&res, H.b.d_result, 1);
-  H.st.back(best_idx, a.d_fuse_out, (size_t)n_list);
-  H.st.back(best_dist, a.d_fuse_out + L, (size_t)n_list);
-  H.st.back(reason, a.d_fuse_out + 2 * L, (size_t)n_list);
+  S.st.back(&res, S.b.d_result, 1);
+  S.st.back(best_idx, a.d_fuse_out, (size_t)n_list);
+  S.st.back(best_dist, a.d_fuse_out + L, (size_t)n_list);
+  S.st.back(reason, a.d_fuse_out + 2 * L, (size_t)n_list);
   int err = 0;
-  if ((rc = H.download(&err))) return rc;
+  if ((rc = S.download(&err))) return rc;
   *n_fused = res.n_fused[0];
   return ORBPL_OK;
 }

@@ -5,26 +5,12 @@
 // pools were packed. With a device present the refusals are still checked.
 // The library's reporters and the camera constants (track_host.cpp) are
 // replaced by stand-ins: they are not what is under test.
-#include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "search_neighbors.hip"
+#include "check_common.h"
 
-namespace {
-std::string g_msg;
-}
-
-int orbpl::hip_fail(hipError_t e, const char* what, int line) {
-  g_msg = std::string(what) + ": " + hipGetErrorString(e);
-  (void)line;
-  return ORBPL_ERR_HIP;
-}
-int orbpl::arg_fail(const char* msg) {
-  g_msg = msg;
-  return ORBPL_ERR_ARG;
-}
 int orbpl::make_consts(const orbpl_camera* cam, const float* scale, const float* inv_sigma2,
                        int nlevels, TrackConsts* out) {
   TrackConsts c{};
@@ -43,40 +29,7 @@ int orbpl::make_consts(const orbpl_camera* cam, const float* scale, const float*
 }
 float orbpl::log_scale_of(const float*, int) { return 0.18232156f; }
 
-#define EXPECT(cond)                                                          \
-  do {                                                                        \
-    if (!(cond)) {                                                            \
-      printf("FAILED line %d: %s (last: %s)\n", __LINE__, #cond, g_msg.c_str()); \
-      return 1;                                                               \
-    }                                                                         \
-  } while (0)
-
 namespace {
-
-// two keyframes of three features, two points: point 0 in both, point 1 in the second
-struct TinyMap {
-  float T[2][16] = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1},
-                    {1, 0, 0, -0.2f, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
-  orbpl_keypoint kp[2][3] = {};
-  float ur[2][3] = {{300, -1, 100}, {290, 50, -1}};
-  uint8_t kdesc[2][3 * 32] = {};
-  int32_t mp[2][3] = {{0, -1, -1}, {0, 1, -1}};
-  int32_t ord[2][2] = {{1, -1}, {0, -1}};
-  orblm_map_keyframe kf[2];
-  float xyz[6] = {0, 0, 4, 0.5f, 0, 5}, normal[6] = {0, 0, 1, 0, 0, 1};
-  float mind[2] = {1, 1}, maxd[2] = {10, 10};
-  uint8_t desc[64] = {}, bad[2] = {0, 0};
-  int32_t ref[2] = {0, 1}, vis[2] = {3, 4}, found[2] = {2, 2}, rep[2], nobs[2], src[4];
-  int16_t obs[128];
-  orblm_map m;
-  TinyMap() {
-    for (int k = 0; k < 2; k++) {
-      for (int i = 0; i < 3; i++) kp[k][i].x = 320.f + 10 * i, kp[k][i].y = 240.f;
-      kf[k] = {10 + k, T[k], 3, kp[k], ur[k], kdesc[k], mp[k], ord[k]};
-    }
-    m = {2, kf, 2, xyz, normal, mind, maxd, desc, ref, bad, vis, found, rep, nobs, obs, src};
-  }
-};
 
 const orbpl_camera kCam = {517.f, 516.f, 318.f, 255.f, 0, 0, 0, 0, 0, 40.f, 3.f, 640, 480};
 const float kScale[8] = {1, 1.2f, 1.44f, 1.728f, 2.0736f, 2.48832f, 2.985984f, 3.5831808f};
@@ -92,22 +45,23 @@ int sin_call(TinyMap& t, int cur = 0, int nlevels = 8) {
 }  // namespace
 
 int main() {
+  // the map of two keyframes
 #define REFUSED(edit, text)                      \
   do {                                           \
-    TinyMap t;                                   \
+    TinyMap t(2);                                \
     edit;                                        \
     EXPECT(sin_call(t) == ORBPL_ERR_ARG);        \
     EXPECT(g_msg == text);                       \
   } while (0)
   REFUSED(t.mp[1][2] = 0, "map point twice in one keyframe");
-  REFUSED(t.kf[1].id = 10, "two keyframes of a map with one id");
+  REFUSED(t.kf[1].id = t.kf[0].id, "two keyframes of a map with one id");
   REFUSED(t.kp[0][2].octave = 8, "keypoint octave outside [0, nlevels)");
   REFUSED(t.mp[0][1] = 2, "slot index outside [-1, M)");
   REFUSED(t.mp[0][1] = -2, "slot index outside [-1, M)");
   REFUSED(t.ref[1] = 0, "good map point whose ref_kf does not observe it");
   REFUSED(t.ref[1] = 77, "good map point whose ref_kf does not observe it");
-  REFUSED(t.ord[0][0] = 2, "ordered entry outside the table or naming its own keyframe");
-  REFUSED(t.ord[1][0] = 1, "ordered entry outside the table or naming its own keyframe");
+  REFUSED(t.kf_ord[0][0] = 2, "ordered entry outside the table or naming its own keyframe");
+  REFUSED(t.kf_ord[1][0] = 1, "ordered entry outside the table or naming its own keyframe");
   REFUSED(t.m.nkf = 65, "map with no keyframe or more than 64");
   REFUSED(t.m.M = 64 * 2048 + 1, "map points outside [0, 64 * 2048]");
   REFUSED(t.m.obs = nullptr, "NULL map point arrays");
@@ -115,7 +69,7 @@ int main() {
   REFUSED(t.kf[0].mp = nullptr, "NULL keyframe arrays");
   REFUSED(t.kf[0].Tcw = nullptr, "NULL keyframe pose");
   {
-    TinyMap t;
+    TinyMap t(2);
     EXPECT(sin_call(t, 2) == ORBPL_ERR_ARG && g_msg == "current keyframe outside the table");
     EXPECT(sin_call(t, 0, 17) == ORBPL_ERR_ARG && g_msg == "nlevels outside [1, 16]");
     orblm_sin_problem two[2] = {};
@@ -136,8 +90,8 @@ int main() {
     return 0;
   }
   {
-    TinyMap t;
-    const TinyMap before;
+    TinyMap t(2);
+    const TinyMap before(2);
     EXPECT(sin_call(t) == ORBPL_ERR_HIP);
     EXPECT(!memcmp(t.mp, before.mp, sizeof(t.mp)) && !memcmp(t.bad, before.bad, sizeof(t.bad)));
     int nf = -1;

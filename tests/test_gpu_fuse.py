@@ -87,15 +87,39 @@ def test_device_pools_bit_equal_to_host_entry(fuser):
 FUSE_CASES = [("n65", "cur_into_first_target"), ("n300", "cur_into_first_target"),
               ("n300", "target_into_cur"), ("hand_tie", "cur_into_first_target"),
               ("hand_conflict", "cur_into_first_target"), ("hand_gates", "cur_into_first_target"),
-              ("mono_mixed", "repeats_and_nulls"), ("n2048", "target_into_cur")]
+              ("mono_mixed", "repeats_and_nulls"), ("n2048", "target_into_cur"), ("tiny", "long_list")]
+
+
+def tiny_problem():
+    """the smallest map: two keyframes of three features, two points; point 0 in
+    both keyframes, point 1 in the second only, where the first sees its corner"""
+    rng = np.random.default_rng(8)
+    X0, X1 = np.array([0.1, 0.05, 4.0]), np.array([-0.3, 0.1, 5.0])
+    d0, d1 = (rng.integers(0, 256, 32, dtype=np.uint8) for _ in range(2))
+
+    def feat(centre, X, d):
+        pu, pv, pz = fp._px(centre, X)
+        return (pu, pv, 0, pu - fp.CAM["bf"] / pz, d)
+
+    ca, cb = [0, 0, 0], [0.2, 0, 0]
+    a = fp._hand_kf(3, ca, [feat(ca, X0, d0), feat(ca, X1, fp._flip(rng, d1, 5)),
+                            (50.0, 60.0, 0, -1.0, fp._flip(rng, d0, 120))])
+    b = fp._hand_kf(8, cb, [feat(cb, X0, fp._flip(rng, d0, 4)), feat(cb, X1, d1),
+                            (90.0, 60.0, 0, -1.0, fp._flip(rng, d1, 120))])
+    a["mp"][:], b["mp"][:] = [0, -1, -1], [0, 1, -1]
+    a["ordered"], b["ordered"] = [1], [0]
+    return fp._finish([a, b], [dict(xyz=X0, ref_kf=0), dict(xyz=X1, ref_kf=1)], 1, [0, 1])
 
 
 @pytest.mark.parametrize("name,case", FUSE_CASES)
 def test_fuse_alone(fuser, name, case):
-    p = fp.problem(name)
+    p = tiny_problem() if name == "tiny" else fp.problem(name)
     m, cur = p["map"], p["cur"]
     first = m["kfs"][cur]["ordered"][0]
-    if case == "cur_into_first_target":
+    if case == "long_list":   # longer than M and the widest keyframe: the list alone sets list_pitch
+        kf, lst = first, [0, -1, 1, -1, 0]
+        assert len(lst) > max(len(m["bad"]), max(len(k["uright"]) for k in m["kfs"]))
+    elif case == "cur_into_first_target":
         kf, lst = first, [int(x) for x in m["kfs"][cur]["mp"]]
     elif case == "target_into_cur":
         kf, lst = cur, [int(x) for x in m["kfs"][first]["mp"] if x >= 0]
