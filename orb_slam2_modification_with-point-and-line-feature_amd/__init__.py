@@ -472,6 +472,57 @@ def _c(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
 
 
+def _pack_rows(arrays, pitch, dtype, row=(), pad=0):
+    """One pitched host column: [max(1, len(arrays)), pitch, *row] of dtype, every
+    element `pad` but the first len(a) entries of row s, which are a = arrays[s]
+    (None fills nothing). pitch None: one entry of shape `row` per row."""
+    out = np.zeros((max(1, len(arrays)),) + (() if pitch is None else (pitch,)) + tuple(row), dtype)
+    if pad:
+        out[...] = pad
+    for s, a in enumerate(arrays):
+        if a is None:
+            continue
+        if pitch is None:
+            out[s] = np.asarray(a).reshape(row)
+        else:
+            a = np.asarray(a).reshape((-1,) + tuple(row))
+            out[s, :len(a)] = a
+    return out
+
+
+def _cols(names, dtype, row=(), pitch=None, pad=0):
+    """column table entries (name, dtype, row shape, pitch key or None, pad)"""
+    return tuple((k, dtype, row, pitch, pad) for k in names.split())
+
+
+class PitchedProblems:
+    """Base of the *DeviceProblems classes over a column table (_cols): pack() makes
+    self.host, the pitched host arrays of the table (cols[name] = the per-row arrays
+    of a column; a column not in cols has `rows` rows of padding, an entry of cols the
+    table lacks is an array taken as it is), and with a device
+    their copies self.bufs and self.batch, the batch struct over them (a d_NAME field
+    is bufs[NAME], any other field is given by name). device None: no buffer, no
+    library call."""
+
+    def pack(self, table, pitches, cols, rows, device, batch, **fields):
+        self.device = device
+        self.host = {k: _pack_rows(cols.get(k, [None] * rows), pitches.get(pk), dt, row, pad)
+                     for k, dt, row, pk, pad in table}
+        self.host.update({k: v for k, v in cols.items() if k not in self.host})
+        if device is None:
+            return
+        self.bufs = {k: DeviceBuffer.from_array(v, device) for k, v in self.host.items()}
+        self.batch = self.struct(batch, **fields)
+
+    def struct(self, cls, **fields):
+        return cls(*[self.bufs[k[2:]].ptr if k.startswith("d_") else fields[k] for k, _ in cls._fields_])
+
+    def fetch(self, *names):
+        """synchronises; the named columns from the device, shaped as self.host's"""
+        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
+        return [self.bufs[k].download(self.host[k].dtype, self.host[k].shape) for k in names]
+
+
 def frame_prepare(camera, kps, depth=None):
     """Frame glue of the RGB-D Frame constructor (Frame.cc:135-205) on the GPU.
     Returns (kps_un, depth, uright, grid_cell, bounds)."""
@@ -1697,73 +1748,51 @@ class PnPsolver:
         return T, vb, n
 
 
-class PnpDeviceProblems:
+_PNP_COLS = (_cols("n min_inliers max_its iterations best_inliers", np.int32) +
+             _cols("cam", np.float32, (4,)) + _cols("best_Tcw", np.float32, (16,)) +
+             _cols("p2d", np.float32, (2,), "pt") + _cols("p3d", np.float32, (3,), "pt") +
+             _cols("max_error", np.float32, (), "pt") + _cols("best_mask", np.uint8, (), "pt") +
+             _cols("draws", np.int32, (), "draw") +
+             # out
+             _cols("result no_more n_inliers draws_consumed", np.int32) +
+             _cols("Tcw", np.float32, (16,)) + _cols("inliers", np.uint8, (), "pt"))
+
+
+class PnpDeviceProblems(PitchedProblems):
     """The pitched device arrays of orbpnp_iterate_batch_device for a list of
     problems (dicts as for pnp_iterate_batch): iterate() launches on the null
     stream without a host round trip, download() synchronises and returns the
     outputs and the state as pnp_iterate_batch does."""
 
     def __init__(self, problems, draw_pitch=4 * PNP_MAX_ITERATIONS, device=0):
-        f32, i32, u8 = np.float32, np.int32, np.uint8
-        self.ns = ns = len(problems)
-        self.n = np.array([len(_c(p["p2d"], f32).reshape(-1, 2)) for p in problems], i32)
-        self.pt_pitch = ptp = max(1, int(self.n.max()) if ns else 1)
+        f32, i32 = np.float32, np.int32
+        self.ns = len(problems)
+        p2d = [_c(p["p2d"], f32).reshape(-1, 2) for p in problems]
+        self.n = np.array([len(a) for a in p2d], i32)
+        self.pt_pitch = max([1] + [len(a) for a in p2d])
         self.draw_pitch = int(draw_pitch)
-        S = max(1, ns)
-        cam = np.zeros((S, 4), f32)
-        p2, p3 = np.zeros((S, ptp, 2), f32), np.zeros((S, ptp, 3), f32)
-        me, dr = np.zeros((S, ptp), f32), np.zeros((S, self.draw_pitch), i32)
-        mn, mx, it, bi = (np.zeros(S, i32) for _ in range(4))
-        bm, bT = np.zeros((S, ptp), u8), np.zeros((S, 16), f32)
-        for s, p in enumerate(problems):
-            n = self.n[s]
-            cam[s] = [float(c) for c in p["cam"]]
-            p2[s, :n] = _c(p["p2d"], f32).reshape(-1, 2)
-            p3[s, :n] = _c(p["p3d"], f32).reshape(-1, 3)
-            me[s, :n] = _c(p["max_error"], f32).reshape(-1)
-            d = _c(p["draws"], i32).reshape(-1)[:self.draw_pitch]
-            dr[s, :len(d)] = d
-            mn[s], mx[s] = p["min_inliers"], p["max_its"]
-            st = p.get("state") or pnp_new_state(n)
-            it[s], bi[s] = st["iterations"], st["best_inliers"]
-            bm[s, :n] = st["best_mask"]
-            bT[s] = _c(st["best_Tcw"], f32).reshape(16)
-        mk = lambda a: DeviceBuffer.from_array(a, device)
-        self.bufs = dict(n=mk(self.n if ns else np.zeros(1, i32)), cam=mk(cam), p2d=mk(p2),
-                         p3d=mk(p3), max_error=mk(me), min_inliers=mk(mn), max_its=mk(mx),
-                         draws=mk(dr), iterations=mk(it), best_inliers=mk(bi), best_mask=mk(bm),
-                         best_Tcw=mk(bT), Tcw=mk(np.zeros((S, 16), f32)),
-                         result=mk(np.zeros(S, i32)), no_more=mk(np.zeros(S, i32)),
-                         n_inliers=mk(np.zeros(S, i32)), inliers=mk(np.zeros((S, ptp), u8)),
-                         draws_consumed=mk(np.zeros(S, i32)))
-        b = self.bufs
-        self.batch = PnpDeviceBatch(b["n"].ptr, b["cam"].ptr, b["p2d"].ptr, b["p3d"].ptr,
-                                    b["max_error"].ptr, ptp, b["min_inliers"].ptr,
-                                    b["max_its"].ptr, b["draws"].ptr, self.draw_pitch,
-                                    b["iterations"].ptr, b["best_inliers"].ptr,
-                                    b["best_mask"].ptr, b["best_Tcw"].ptr, b["Tcw"].ptr,
-                                    b["result"].ptr, b["no_more"].ptr, b["n_inliers"].ptr,
-                                    b["inliers"].ptr, b["draws_consumed"].ptr)
-        self.device = device
+        st = [p.get("state") or pnp_new_state(len(a)) for p, a in zip(problems, p2d)]
+        cols = dict(n=self.n, p2d=p2d, cam=[[float(c) for c in p["cam"]] for p in problems],
+                    draws=[_c(p["draws"], i32).reshape(-1)[:self.draw_pitch] for p in problems],
+                    best_Tcw=[_c(t["best_Tcw"], f32) for t in st])
+        cols.update({k: [p[k] for p in problems] for k in ("p3d", "max_error", "min_inliers", "max_its")})
+        cols.update({k: [t[k] for t in st] for k in ("iterations", "best_inliers", "best_mask")})
+        self.pack(_PNP_COLS, dict(pt=self.pt_pitch, draw=self.draw_pitch), cols, self.ns, device,
+                  PnpDeviceBatch, pt_pitch=self.pt_pitch, draw_pitch=self.draw_pitch)
 
     def iterate(self, n_iterations, stream=None):
         check(lib().orbpnp_iterate_batch_device(C.byref(self.batch), self.ns, int(n_iterations),
                                                 stream), "orbpnp_iterate_batch_device")
 
     def download(self):
-        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
-        S, ptp, b = max(1, self.ns), self.pt_pitch, self.bufs
-        i32 = np.int32
-        res, nm = b["result"].download(i32, S), b["no_more"].download(i32, S)
-        ni, dc = b["n_inliers"].download(i32, S), b["draws_consumed"].download(i32, S)
-        it, bi = b["iterations"].download(i32, S), b["best_inliers"].download(i32, S)
-        inl, bm = (b[k].download(np.uint8, (S, ptp)) for k in ("inliers", "best_mask"))
-        T, bT = (b[k].download(np.float32, (S, 4, 4)) for k in ("Tcw", "best_Tcw"))
+        res, nm, ni, dc, it, bi, inl, bm, T, bT = self.fetch(
+            "result", "no_more", "n_inliers", "draws_consumed", "iterations", "best_inliers",
+            "inliers", "best_mask", "Tcw", "best_Tcw")
         return [dict(result=int(res[s]), no_more=bool(nm[s]), n_inliers=int(ni[s]),
-                     inliers=inl[s, :self.n[s]].astype(bool), Tcw=T[s].copy(),
+                     inliers=inl[s, :self.n[s]].astype(bool), Tcw=T[s].reshape(4, 4).copy(),
                      draws_consumed=int(dc[s]),
                      state=dict(iterations=int(it[s]), best_inliers=int(bi[s]),
-                                best_mask=bm[s, :self.n[s]].copy(), best_Tcw=bT[s].copy()))
+                                best_mask=bm[s, :self.n[s]].copy(), best_Tcw=bT[s].reshape(4, 4).copy()))
                 for s in range(self.ns)]
 
 
@@ -1998,7 +2027,21 @@ class Sim3Solver:
         return np.float32(self.state["best_s"])
 
 
-class Sim3DeviceProblems:
+_SIM3_COLS = (_cols("n1 n2 min_inliers fix_scale", np.int32) + _cols("cam", np.float32, (4,)) +
+              _cols("Tcw1 Tcw2", np.float32, (16,)) + _cols("matched12", np.int32, (), "p1", -1) +
+              _cols("valid1", np.uint8, (), "p1") + _cols("valid2", np.uint8, (), "p2") +
+              _cols("xyz1", np.float32, (3,), "p1") + _cols("xyz2", np.float32, (3,), "p2") +
+              _cols("octave1", np.int32, (), "p1") + _cols("octave2", np.int32, (), "p2") +
+              _cols("draws", np.int32, (), "draw") +
+              # out (max_its: 1 until setup() has the table's value)
+              _cols("n iterations best_inliers result no_more n_inliers draws_consumed", np.int32) +
+              _cols("max_its", np.int32, pad=1) + _cols("indices1", np.int32, (), "p1") +
+              _cols("best_mask inliers", np.uint8, (), "p1") + _cols("T12", np.float32, (16,)) +
+              tuple((k, dt, (w,), "p1", 0) for k, dt, w in _SIM3_CORR) +
+              tuple((k, np.float32, (w,), None, 0) for k, w in _SIM3_STATE))
+
+
+class Sim3DeviceProblems(PitchedProblems):
     """The pitched device arrays of orbsim3_setup_batch_device and
     orbsim3_iterate_batch_device for a list of keyframe pairs (dicts as for
     sim3_setup, plus ``fix_scale``, ``draws`` and optionally ``min_inliers``):
@@ -2009,63 +2052,29 @@ class Sim3DeviceProblems:
 
     def __init__(self, pairs, level_sigma2, probability=0.99, minInliers=6, maxIterations=300,
                  draw_pitch=3 * SIM3_MAX_ITERATIONS, device=0):
-        f32, i32, u8 = np.float32, np.int32, np.uint8
-        self.ns = ns = len(pairs)
-        self.device, self.draw_pitch = device, int(draw_pitch)
+        i32 = np.int32
+        self.ns = len(pairs)
+        self.draw_pitch = int(draw_pitch)
         self.params = (probability, maxIterations)
-        S = max(1, ns)
         arrs = [_sim3_pair_arrays(p) for p in pairs]
         self.n1 = np.array([a[1] for a in arrs] or [0], i32)
         self.n2 = np.array([a[2] for a in arrs] or [0], i32)
         self.pitch1 = p1 = max(1, int(self.n1.max()))
         self.pitch2 = p2 = max(1, int(self.n2.max()))
-        sig = _c(level_sigma2, f32).reshape(-1)
-        h = dict(n1=self.n1, n2=self.n2, matched12=np.full((S, p1), -1, i32),
-                 valid1=np.zeros((S, p1), u8), xyz1=np.zeros((S, p1, 3), f32),
-                 octave1=np.zeros((S, p1), i32), valid2=np.zeros((S, p2), u8),
-                 xyz2=np.zeros((S, p2, 3), f32), octave2=np.zeros((S, p2), i32),
-                 Tcw1=np.zeros((S, 16), f32), Tcw2=np.zeros((S, 16), f32),
-                 cam=np.zeros((S, 4), f32), level_sigma2=sig,
-                 min_inliers=np.full(S, int(minInliers), i32), fix_scale=np.zeros(S, i32),
-                 draws=np.zeros((S, self.draw_pitch), i32))
-        for s, ((a, n1, n2, cam), p) in enumerate(zip(arrs, pairs)):
-            for k in ("matched12", "valid1", "xyz1", "octave1"):
-                h[k][s, :n1] = a[k]
-            for k in ("valid2", "xyz2", "octave2"):
-                h[k][s, :n2] = a[k]
-            h["Tcw1"][s], h["Tcw2"][s], h["cam"][s] = a["Tcw1"], a["Tcw2"], cam
-            h["min_inliers"][s] = p.get("min_inliers", minInliers)
-            h["fix_scale"][s] = bool(p.get("fix_scale", False))
-            d = _c(p.get("draws", ()), i32).reshape(-1)[:self.draw_pitch]
-            h["draws"][s, :len(d)] = d
+        sig = _c(level_sigma2, np.float32).reshape(-1)
         self.nlevels = len(sig)
-        z = dict(n=np.zeros(S, i32), indices1=np.zeros((S, p1), i32), max_its=np.ones(S, i32),
-                 iterations=np.zeros(S, i32), best_inliers=np.zeros(S, i32),
-                 best_mask=np.zeros((S, p1), u8), T12=np.zeros((S, 16), f32),
-                 result=np.zeros(S, i32), no_more=np.zeros(S, i32), n_inliers=np.zeros(S, i32),
-                 inliers=np.zeros((S, p1), u8), draws_consumed=np.zeros(S, i32))
-        for k, dt, w in _SIM3_CORR:
-            z[k] = np.zeros((S, p1, w), dt)
-        for k, w in _SIM3_STATE:
-            z[k] = np.zeros((S, w), f32)
-        self.bufs = b = {k: DeviceBuffer.from_array(v, device) for k, v in {**h, **z}.items()}
-        self.setup_batch = Sim3SetupDeviceBatch(
-            b["n1"].ptr, b["n2"].ptr, p1, p2,
-            *[b[k].ptr for k in ("matched12", "valid1", "xyz1", "octave1", "valid2", "xyz2",
-                                 "octave2", "Tcw1", "Tcw2", "cam", "level_sigma2")],
-            self.nlevels,
-            *[b[k].ptr for k in ("n", "indices1", "X3Dc1", "X3Dc2", "P1im1", "P2im2",
-                                 "max_error1", "max_error2")])
-        self.batch = Sim3DeviceBatch(
-            *[b[k].ptr for k in ("n", "cam", "X3Dc1", "X3Dc2", "P1im1", "P2im2", "max_error1",
-                                 "max_error2")], p1,
-            *[b[k].ptr for k in ("min_inliers", "max_its", "fix_scale", "draws")],
-            self.draw_pitch,
-            *[b[k].ptr for k in ("iterations", "best_inliers", "best_mask", "best_T12", "best_R",
-                                 "best_t", "best_s", "T12", "result", "no_more", "n_inliers",
-                                 "inliers", "draws_consumed")])
-        self.min_inliers = h["min_inliers"]
+        cols = {k: [a[0][k] for a in arrs] for k in ("matched12", "valid1", "xyz1", "octave1", "valid2",
+                                                     "xyz2", "octave2", "Tcw1", "Tcw2")}
+        cols.update(n1=self.n1[:self.ns], n2=self.n2[:self.ns], cam=[a[3] for a in arrs], level_sigma2=sig,
+                    min_inliers=[p.get("min_inliers", minInliers) for p in pairs],
+                    fix_scale=[bool(p.get("fix_scale", False)) for p in pairs],
+                    draws=[_c(p.get("draws", ()), i32).reshape(-1)[:self.draw_pitch] for p in pairs])
+        self.pack(_SIM3_COLS, dict(p1=p1, p2=p2, draw=self.draw_pitch), cols, self.ns, device,
+                  Sim3DeviceBatch, pt_pitch=p1, draw_pitch=self.draw_pitch)
+        self.min_inliers = self.host["min_inliers"]
         self.n = None
+        if device is not None:
+            self.setup_batch = self.struct(Sim3SetupDeviceBatch, pitch1=p1, pitch2=p2, nlevels=self.nlevels)
 
     def setup(self, stream=None):
         """the constructor kernel, then SetRansacParameters per solver on the
@@ -2087,32 +2096,27 @@ class Sim3DeviceProblems:
                                                  stream), "orbsim3_iterate_batch_device")
 
     def download(self):
-        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
-        S, p1, b = max(1, self.ns), self.pitch1, self.bufs
-        i32, f32 = np.int32, np.float32
-        g = {k: b[k].download(i32, S) for k in ("n", "result", "no_more", "n_inliers",
-                                                "draws_consumed", "iterations", "best_inliers")}
-        ind = b["indices1"].download(i32, (S, p1))
-        inl, bm = (b[k].download(np.uint8, (S, p1)) for k in ("inliers", "best_mask"))
-        co = {k: b[k].download(dt, (S, p1, w)) for k, dt, w in _SIM3_CORR}
-        sv = {k: b[k].download(f32, (S, w)) for k, w in _SIM3_STATE}
-        T = b["T12"].download(f32, (S, 4, 4))
+        names = ("n", "result", "no_more", "n_inliers", "draws_consumed", "iterations", "best_inliers",
+                 "indices1", "inliers", "best_mask", "T12") + tuple(k for k, _, _ in _SIM3_CORR) + \
+            tuple(k for k, _ in _SIM3_STATE)
+        g = dict(zip(names, self.fetch(*names)))
         out = []
         for s in range(self.ns):
             n = int(g["n"][s])
-            corr = dict(n=n, indices1=ind[s, :n].copy())
+            corr = dict(n=n, indices1=g["indices1"][s, :n].copy())
             for k, dt, w in _SIM3_CORR:
-                corr[k] = co[k][s, :n].reshape((n, w) if w > 1 else n).copy()
+                corr[k] = g[k][s, :n].reshape((n, w) if w > 1 else n).copy()
             out.append(dict(corr=corr, result=int(g["result"][s]), no_more=bool(g["no_more"][s]),
-                            n_inliers=int(g["n_inliers"][s]), inliers=inl[s, :n].astype(bool),
-                            T12=T[s].copy(), draws_consumed=int(g["draws_consumed"][s]),
+                            n_inliers=int(g["n_inliers"][s]), inliers=g["inliers"][s, :n].astype(bool),
+                            T12=g["T12"][s].reshape(4, 4).copy(),
+                            draws_consumed=int(g["draws_consumed"][s]),
                             state=dict(iterations=int(g["iterations"][s]),
                                        best_inliers=int(g["best_inliers"][s]),
-                                       best_mask=bm[s, :n].copy(),
-                                       best_T12=sv["best_T12"][s].reshape(4, 4).copy(),
-                                       best_R=sv["best_R"][s].reshape(3, 3).copy(),
-                                       best_t=sv["best_t"][s].copy(),
-                                       best_s=np.float32(sv["best_s"][s, 0]))))
+                                       best_mask=g["best_mask"][s, :n].copy(),
+                                       best_T12=g["best_T12"][s].reshape(4, 4).copy(),
+                                       best_R=g["best_R"][s].reshape(3, 3).copy(),
+                                       best_t=g["best_t"][s].copy(),
+                                       best_s=np.float32(g["best_s"][s, 0]))))
         return out
 
 
@@ -2190,46 +2194,34 @@ def search_by_sim3_batch(camera, scale_factors, pairs, th):
                  reason1=r1[:n1], reason2=r2[:n2]) for n1, n2, m, nf, v1, v2, r1, r2 in outs]
 
 
-class Sim3MatchDeviceProblems:
+_SBS_COLS = (tuple(("%s%d" % (k, side), dt, w, side, 0) for side in (1, 2) for k, dt, w in _SBS_KF) +
+             _cols("Tcw1 Tcw2", np.float32, (16,)) + _cols("n1 n2", np.int32) +
+             _cols("s12", np.float32) + _cols("R12", np.float32, (9,)) + _cols("t12", np.float32, (3,)) +
+             _cols("matched12", np.int32, (), 1, -1) +
+             # out
+             _cols("n_found", np.int32) + _cols("vn_match1 reason1", np.int32, (), 1) +
+             _cols("vn_match2 reason2", np.int32, (), 2))
+
+
+class Sim3MatchDeviceProblems(PitchedProblems):
     """The pitched device arrays of orbm_search_by_sim3_batch_device for a list
     of pairs (dicts as for search_by_sim3_batch): run() launches without a
     host round trip, download() synchronises and returns what
     search_by_sim3_batch returns."""
 
     def __init__(self, pairs, device=0):
-        f32, i32 = np.float32, np.int32
-        self.ns = ns = len(pairs)
-        self.device = device
-        S = max(1, ns)
+        self.ns = len(pairs)
         ks = [(_sbs_keyframe(p["kf1"]), _sbs_keyframe(p["kf2"])) for p in pairs]
-        self.n1 = np.array([k[0][1] for k in ks] or [0], i32)
-        self.n2 = np.array([k[1][1] for k in ks] or [0], i32)
+        self.n1 = np.array([k[0][1] for k in ks] or [0], np.int32)
+        self.n2 = np.array([k[1][1] for k in ks] or [0], np.int32)
         self.pitch = pt = (max(1, int(self.n1.max())), max(1, int(self.n2.max())))
-        h = dict(n1=self.n1, n2=self.n2, s12=np.zeros(S, f32), R12=np.zeros((S, 9), f32),
-                 t12=np.zeros((S, 3), f32), matched12=np.full((S, pt[0]), -1, i32))
-        for side in (1, 2):
-            for k, dt, w in _SBS_KF:
-                h["%s%d" % (k, side)] = np.zeros((S, pt[side - 1]) + w, dt)
-            h["Tcw%d" % side] = np.zeros((S, 16), f32)
-        for s, (p, kk) in enumerate(zip(pairs, ks)):
-            for side, (a, n) in zip((1, 2), kk):
-                for k, _, _ in _SBS_KF:
-                    h["%s%d" % (k, side)][s, :n] = a[k]
-                h["Tcw%d" % side][s] = a["Tcw"]
-            h["s12"][s] = p["s12"]
-            h["R12"][s] = _c(p["R12"], f32).reshape(9)
-            h["t12"][s] = _c(p["t12"], f32).reshape(3)
-            h["matched12"][s, :self.n1[s]] = _c(p["matched12"], i32).reshape(-1)
-        self.host_matched12 = h["matched12"]     # to restore the in/out array between runs
-        z = dict(n_found=np.zeros(S, i32), vn_match1=np.zeros((S, pt[0]), i32),
-                 vn_match2=np.zeros((S, pt[1]), i32), reason1=np.zeros((S, pt[0]), i32),
-                 reason2=np.zeros((S, pt[1]), i32))
-        self.bufs = b = {k: DeviceBuffer.from_array(v, device) for k, v in {**h, **z}.items()}
-        self.batch = Sim3MatchDeviceBatch(
-            b["n1"].ptr, b["n2"].ptr, pt[0], pt[1],
-            *[b["%s%d" % (k, s)].ptr for s in (1, 2) for k in [k for k, _, _ in _SBS_KF] + ["Tcw"]],
-            *[b[k].ptr for k in ("s12", "R12", "t12", "matched12", "n_found", "vn_match1",
-                                 "vn_match2", "reason1", "reason2")])
+        cols = {"%s%d" % (k, side): [kk[side - 1][0][k] for kk in ks]
+                for side in (1, 2) for k in [k for k, _, _ in _SBS_KF] + ["Tcw"]}
+        cols.update({k: [p[k] for p in pairs] for k in ("s12", "R12", "t12", "matched12")})
+        cols.update(n1=self.n1[:self.ns], n2=self.n2[:self.ns])
+        self.pack(_SBS_COLS, {1: pt[0], 2: pt[1]}, cols, self.ns, device, Sim3MatchDeviceBatch,
+                  pitch1=pt[0], pitch2=pt[1])
+        self.host_matched12 = self.host["matched12"]     # to restore the in/out array between runs
 
     def run(self, camera, scale_factors, th, stream=None):
         sf = _c(scale_factors, np.float32)
@@ -2238,11 +2230,8 @@ class Sim3MatchDeviceProblems:
                                                      stream), "orbm_search_by_sim3_batch_device")
 
     def download(self):
-        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
-        S, pt, b, i32 = max(1, self.ns), self.pitch, self.bufs, np.int32
-        nf = b["n_found"].download(i32, S)
-        m, v1, r1 = (b[k].download(i32, (S, pt[0])) for k in ("matched12", "vn_match1", "reason1"))
-        v2, r2 = (b[k].download(i32, (S, pt[1])) for k in ("vn_match2", "reason2"))
+        nf, m, v1, r1, v2, r2 = self.fetch("n_found", "matched12", "vn_match1", "reason1", "vn_match2",
+                                           "reason2")
         return [dict(n_found=int(nf[s]), matched12=m[s, :self.n1[s]].copy(),
                      vn_match1=v1[s, :self.n1[s]].copy(), vn_match2=v2[s, :self.n2[s]].copy(),
                      reason1=r1[s, :self.n1[s]].copy(), reason2=r2[s, :self.n2[s]].copy())
@@ -2621,7 +2610,21 @@ def search_for_triangulation(camera, scale_factors, level_sigma2, kf1, kf2, only
         kf1, kf2, only_stereo, check_ori)
 
 
-class LmDeviceProblems:
+_LM_COLS = (_cols("kf_id kf_n kf_nl", np.int32) + _cols("kf_Tcw", np.float32, (16,)) +
+            _cols("kps kps_un", KP_DTYPE, (), "P") + _cols("uright depth", np.float32, (), "P", -1) +
+            _cols("desc", np.uint8, (32,), "P") + _cols("feat_node", np.int32, (), "P", -1) +
+            _cols("has_mp", np.uint8, (), "P", 1) + _cols("mp_xyz", np.float32, (3,), "P") +
+            _cols("klines", KEYLINE_DTYPE, (), "LP") + _cols("ldesc", np.uint8, (32,), "LP") +
+            _cols("lcoef", np.float64, (3,), "LP") +
+            # per problem: the pool indices, then out
+            _cols("cur", np.int32) + _cols("neigh", np.int32, (), "NB", -1) +
+            _cols("points", LM_RECORD_DTYPE, (), "P") + _cols("lines", LM_LINE_RECORD_DTYPE, (), "NLP") +
+            _cols("n_points n_lines", np.int32) + _cols("kf1_point_record", np.int32, (), "P") +
+            _cols("kf1_line_record", np.int32, (), "LP") +
+            _cols("pairs line_pairs", np.int32, (LM_MAX_NEIGHBOURS,)))
+
+
+class LmDeviceProblems(PitchedProblems):
     """The pitched device pool of orblm_create_new_map_features_batch_device for
     a list of problems (as LocalMapper.create_new_map_features takes them): run()
     launches without a host round trip, download() synchronises and returns the
@@ -2629,16 +2632,13 @@ class LmDeviceProblems:
     one pool (problems are indices into it)."""
 
     def __init__(self, mapper, problems, device=0, repeat=1):
-        self.mapper, self.device, self.ns = mapper, device, len(problems) * repeat
+        self.mapper, self.ns = mapper, len(problems) * repeat
         kfs, cur, neigh = [], [], []
         for prob in problems:
             cur.append(len(kfs))
             kfs.append(prob["cur"])
-            row = [-1] * LM_MAX_NEIGHBOURS
-            for k, kf in enumerate(prob["neigh"]):
-                row[k] = len(kfs)
-                kfs.append(kf)
-            neigh.append(row)
+            neigh.append([len(kfs) + k for k in range(len(prob["neigh"]))])
+            kfs += list(prob["neigh"])
         cur, neigh = cur * repeat, neigh * repeat
         arrs = [_lm_arrays(k) for k in kfs]
         ns, nls = [a[0] for a in arrs], [a[1] for a in arrs]
@@ -2646,39 +2646,11 @@ class LmDeviceProblems:
         self.nl1 = [nls[c] for c in cur]
         self.pitch = P = max([1] + ns)
         self.line_pitch = LP = max([1] + nls)
-        K, S = max(1, len(kfs)), max(1, self.ns)
-        host = dict(kps=np.zeros((K, P), KP_DTYPE), kps_un=np.zeros((K, P), KP_DTYPE),
-                    uright=np.full((K, P), -1, np.float32), depth=np.full((K, P), -1, np.float32),
-                    desc=np.zeros((K, P, 32), np.uint8), feat_node=np.full((K, P), -1, np.int32),
-                    has_mp=np.ones((K, P), np.uint8), mp_xyz=np.zeros((K, P, 3), np.float32),
-                    klines=np.zeros((K, LP), KEYLINE_DTYPE), ldesc=np.zeros((K, LP, 32), np.uint8),
-                    lcoef=np.zeros((K, LP, 3), np.float64))
-        T, ids = np.zeros((K, 16), np.float32), np.zeros(K, np.int32)
-        for k, kf in enumerate(kfs):
-            T[k], ids[k] = _c(kf["Tcw"], np.float32).reshape(16), int(kf["id"])
-            for name in _LM_POINT_FIELDS:
-                host[name][k, :ns[k]] = arrs[k][2][name]
-            for name in _LM_LINE_FIELDS:
-                host[name][k, :nls[k]] = arrs[k][2][name]
-        mk = lambda a: DeviceBuffer.from_array(a, device)
-        pad = lambda v, n: np.array(list(v) + [0] * (n - len(v)), np.int32)
-        NB = LM_MAX_NEIGHBOURS
-        b = self.bufs = dict(id=mk(ids), n=mk(pad(ns, K)), nl=mk(pad(nls, K)), T=mk(T),
-                             cur=mk(pad(cur, S)), neigh=mk(np.array(neigh or [[-1] * NB], np.int32)),
-                             points=DeviceBuffer(S * P * LM_RECORD_DTYPE.itemsize, device),
-                             n_points=DeviceBuffer(S * 4, device), rec=DeviceBuffer(S * P * 4, device),
-                             pairs=DeviceBuffer(S * NB * 4, device),
-                             lines=DeviceBuffer(S * NB * LP * LM_LINE_RECORD_DTYPE.itemsize, device),
-                             n_lines=DeviceBuffer(S * 4, device), lrec=DeviceBuffer(S * LP * 4, device),
-                             lpairs=DeviceBuffer(S * NB * 4, device),
-                             **{k: mk(v) for k, v in host.items()})
-        self.batch = LmDeviceBatch(K, P, LP, b["id"].ptr, b["n"].ptr, b["T"].ptr, b["kps"].ptr,
-                                   b["kps_un"].ptr, b["uright"].ptr, b["depth"].ptr, b["desc"].ptr,
-                                   b["feat_node"].ptr, b["has_mp"].ptr, b["mp_xyz"].ptr, b["nl"].ptr,
-                                   b["klines"].ptr, b["ldesc"].ptr, b["lcoef"].ptr, b["cur"].ptr,
-                                   b["neigh"].ptr, b["points"].ptr, b["n_points"].ptr, b["rec"].ptr,
-                                   b["pairs"].ptr, b["lines"].ptr, b["n_lines"].ptr, b["lrec"].ptr,
-                                   b["lpairs"].ptr)
+        cols = {k: [a[2][k] for a in arrs] for k in _LM_POINT_FIELDS + _LM_LINE_FIELDS}
+        cols.update(kf_id=[int(k["id"]) for k in kfs], kf_n=ns, kf_nl=nls, kf_Tcw=[k["Tcw"] for k in kfs],
+                    cur=cur, neigh=neigh)
+        self.pack(_LM_COLS, dict(P=P, LP=LP, NB=LM_MAX_NEIGHBOURS, NLP=LM_MAX_NEIGHBOURS * LP), cols, self.ns, device,
+                  LmDeviceBatch, nkf=max(1, len(kfs)), kp_pitch=P, line_pitch=LP)
 
     def run(self, stream=None):
         check(lib().orblm_create_new_map_features_batch_device(
@@ -2686,15 +2658,9 @@ class LmDeviceProblems:
             "orblm_create_new_map_features_batch_device")
 
     def download(self):
-        check(lib().orbpl_device_synchronize(self.device), "orbpl_device_synchronize")
-        S, P, LP, b, NB = max(1, self.ns), self.pitch, self.line_pitch, self.bufs, LM_MAX_NEIGHBOURS
-        npts, nlns = b["n_points"].download(np.int32, S), b["n_lines"].download(np.int32, S)
-        pts = b["points"].download(LM_RECORD_DTYPE, (S, P))
-        rec = b["rec"].download(np.int32, (S, P))
-        pairs = b["pairs"].download(np.int32, (S, NB))
-        lns = b["lines"].download(LM_LINE_RECORD_DTYPE, (S, NB * LP))
-        lrec = b["lrec"].download(np.int32, (S, LP))
-        lpairs = b["lpairs"].download(np.int32, (S, NB))
+        npts, nlns, pts, rec, pairs, lns, lrec, lpairs = self.fetch(
+            "n_points", "n_lines", "points", "kf1_point_record", "pairs", "lines", "kf1_line_record",
+            "line_pairs")
         return [_lm_outputs(self.n1[s], self.nl1[s], int(npts[s]), pts[s], rec[s], pairs[s],
                             int(nlns[s]), lns[s], lrec[s], lpairs[s]) for s in range(self.ns)]
 

@@ -1,8 +1,11 @@
 // HIP_CHECK, and the device staging of the synchronous host-pointer entry
-// points: HostStage owns the device arrays of one such call.
+// points: Rows is one pitched column of such a call on the host, HostStage owns
+// the device arrays of the call.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cassert>
 #include <cstddef>
 #include <vector>
 
@@ -16,6 +19,34 @@
   } while (0)
 
 namespace orbpl {
+
+// One column of a batched call: `rows` rows of `row` elements of T, every
+// element `pad` until something fills it; d is the device array once a
+// HostStage staged the column. The row length is stated here and nowhere else:
+// put and take address a row by its number and refuse to pass its end.
+template <class T>
+struct Rows {
+  size_t rows = 0, row = 0;
+  std::vector<T> h;
+  T* d = nullptr;
+
+  Rows() = default;
+  Rows(size_t rows_, size_t row_, T pad = T()) : rows(rows_), row(row_), h(rows_ * row_, pad) {}
+  // element i of row r; at(p) is problem p's entry of a one-per-problem column
+  T& at(size_t r, size_t i = 0) {
+    assert(r < rows && i < row);
+    return h[r * row + i];
+  }
+  // the first n elements of row r from src / to dst (NULL allowed when n == 0)
+  void put(size_t r, const T* src, size_t n) {
+    assert(n <= row && (n == 0 || r < rows));
+    if (n) std::copy(src, src + n, h.begin() + r * row);
+  }
+  void take(size_t r, T* dst, size_t n) const {
+    assert(n <= row && (n == 0 || r < rows));
+    if (n) std::copy(h.begin() + r * row, h.begin() + r * row + n, dst);
+  }
+};
 
 // One hipMalloc per array (an overrun faults instead of reaching a neighbour),
 // blocking copies, counts and capacities in elements of T. The first HIP
@@ -76,6 +107,35 @@ class HostStage {
   void back(std::vector<T>& h, const T* d, int line = __builtin_LINE()) {
     back(h.data(), d, h.size(), line);
   }
+  // a column: staged from (in), sized as (out), zeroed as (zeros) or copied back
+  // into (back) its host vector. out, zeros and inout remember the column:
+  // back_outs copies every remembered column back
+  template <class T>
+  T* in(Rows<T>& c, int line = __builtin_LINE()) {
+    return c.d = in(c.h, line);
+  }
+  template <class T>
+  T* inout(Rows<T>& c, int line = __builtin_LINE()) {
+    outs_.push_back({c.h.data(), in(c, line), c.h.size() * sizeof(T)});
+    return c.d;
+  }
+  template <class T>
+  T* out(Rows<T>& c, int line = __builtin_LINE()) {
+    outs_.push_back({c.h.data(), c.d = out<T>(c.h.size(), line), c.h.size() * sizeof(T)});
+    return c.d;
+  }
+  template <class T>
+  T* zeros(Rows<T>& c, int line = __builtin_LINE()) {
+    outs_.push_back({c.h.data(), c.d = zeros<T>(c.h.size(), line), c.h.size() * sizeof(T)});
+    return c.d;
+  }
+  template <class T>
+  void back(Rows<T>& c, int line = __builtin_LINE()) {
+    back(c.h, c.d, line);
+  }
+  void back_outs(int line = __builtin_LINE()) {
+    for (const Out& o : outs_) back(static_cast<char*>(o.h), static_cast<const char*>(o.d), o.bytes, line);
+  }
   // after the launch: folds in hipGetLastError()
   int launched(int line = __builtin_LINE()) {
     if (!rc_) ok(hipGetLastError(), "hipGetLastError()", line);
@@ -88,7 +148,13 @@ class HostStage {
     if (e != hipSuccess) rc_ = hip_fail(e, what, line);
     return e == hipSuccess;
   }
+  struct Out {
+    void* h;
+    const void* d;
+    size_t bytes;
+  };
   std::vector<void*> bufs_;
+  std::vector<Out> outs_;
   int rc_ = ORBPL_OK;
 };
 

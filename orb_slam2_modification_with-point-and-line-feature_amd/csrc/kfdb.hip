@@ -25,6 +25,7 @@
 
 #include "../../include/orbpl.h"
 #include "block_ops.h"
+#include "host_rows.h"
 #include "host_stage.h"
 #include "orbpl_runtime.h"
 #include "reloc_kernels.h"
@@ -243,77 +244,31 @@ int orbkf_detect_reloc(const orbkf_problem* P, int nq, int scoring) {
   if (nq == 0) return ORBPL_OK;
   size_t entp = 1, qp = 1;
   for (int p = 0; p < nq; p++) {
-    const orbkf_problem& r = P[p];
-    if (r.nkf < 0 || r.nkf > kKfdbMaxKf) return arg_fail("more than 64 keyframes in a database");
-    if (r.nq_words < 0 || r.nq_words > kKfdbMaxWords)
-      return arg_fail("more than 4096 entries in the query's BowVector");
-    if (!r.cand || !r.ncand) return arg_fail("NULL output");
-    if (r.nq_words > 0 && (!r.q_words || !r.q_vals)) return arg_fail("NULL query BowVector");
-    if (r.nkf > 0) {
-      if (!r.kf_off || !r.covis || !r.reloc_score) return arg_fail("NULL keyframe arrays");
-      if (r.kf_off[0] != 0) return arg_fail("kf_off[0] != 0");
-      for (int k = 0; k < r.nkf; k++) {
-        const int len = r.kf_off[k + 1] - r.kf_off[k];
-        if (len < 0 || len > kKfdbMaxWords)
-          return arg_fail("a keyframe's BowVector has a negative length or more than 4096 entries");
-      }
-      if (r.kf_off[r.nkf] > 0 && (!r.kf_words || !r.kf_vals))
-        return arg_fail("NULL keyframe BowVectors");
-      entp = std::max(entp, (size_t)r.kf_off[r.nkf]);
-    }
-    qp = std::max(qp, (size_t)r.nq_words);
+    if (const char* no = kfdb_refusal(P[p], "kf_off[0] != 0", &entp, &qp)) return arg_fail(no);
+    if (!P[p].cand || !P[p].ncand) return arg_fail("NULL output");
   }
-  const size_t Q = nq, K = kKfdbMaxKf;
-  std::vector<int> h_nkf(Q), h_off(Q * (K + 1), 0), h_cov(Q * K * kKfdbCovis, -1), h_qn(Q);
-  std::vector<uint32_t> h_kw(Q * entp, 0), h_qw(Q * qp, 0);
-  std::vector<double> h_kv(Q * entp, 0), h_qv(Q * qp, 0);
-  std::vector<float> h_rs(Q * K, 0.0f);
-  for (size_t p = 0; p < Q; p++) {
-    const orbkf_problem& r = P[p];
-    h_nkf[p] = r.nkf;
-    h_qn[p] = r.nq_words;
-    std::copy(r.q_words, r.q_words + r.nq_words, h_qw.begin() + p * qp);
-    std::copy(r.q_vals, r.q_vals + r.nq_words, h_qv.begin() + p * qp);
-    if (!r.nkf) continue;
-    std::copy(r.kf_off, r.kf_off + r.nkf + 1, h_off.begin() + p * (K + 1));
-    const int ne = r.kf_off[r.nkf];
-    std::copy(r.kf_words, r.kf_words + ne, h_kw.begin() + p * entp);
-    std::copy(r.kf_vals, r.kf_vals + ne, h_kv.begin() + p * entp);
-    std::copy(r.covis, r.covis + r.nkf * kKfdbCovis, h_cov.begin() + p * K * kKfdbCovis);
-    std::copy(r.reloc_score, r.reloc_score + r.nkf, h_rs.begin() + p * K);
-  }
+  KfdbCallRows R(P, nq, entp, qp);
   HostStage st;
-  KfdbArgs a{st.in(h_nkf),
-             st.in(h_off),
-             st.in(h_kw),
-             st.in(h_kv),
+  KfdbArgs a{st.in(R.db.nkf),
+             st.in(R.db.kf_off),
+             st.in(R.db.kf_words),
+             st.in(R.db.kf_vals),
              (long long)entp,
-             st.in(h_cov),
-             st.in(h_rs),
-             st.in(h_qn),
-             st.in(h_qw),
-             st.in(h_qv),
+             st.in(R.db.covis),
+             st.inout(R.db.reloc_score),
+             st.in(R.db.q_n),
+             st.in(R.db.q_words),
+             st.in(R.db.q_vals),
              (long long)qp,
-             st.out<int>(Q * K),
-             st.out<int>(Q),
-             st.zeros<int>(Q * K)};
+             st.out(R.cand),
+             st.out(R.ncand),
+             st.zeros(R.common_words)};
   if (st.rc()) return st.rc();
   launch_kfdb_reloc(a, nq, nullptr);   // host-pointer APIs use the null stream
   st.launched();
-  std::vector<int> h_cand(Q * K), h_nc(Q), h_cw(Q * K);
-  st.back(h_cand, a.cand);
-  st.back(h_nc, a.ncand);
-  st.back(h_cw, a.common_words);
-  st.back(h_rs, a.reloc_score);
+  st.back_outs();
   if (st.rc()) return st.rc();
-  for (size_t p = 0; p < Q; p++) {
-    const orbkf_problem& r = P[p];
-    *r.ncand = h_nc[p];
-    std::copy(h_cand.begin() + p * K, h_cand.begin() + p * K + h_nc[p], r.cand);
-    if (r.nkf) std::copy(h_rs.begin() + p * K, h_rs.begin() + p * K + r.nkf, r.reloc_score);
-    if (r.common_words)
-      std::copy(h_cw.begin() + p * K, h_cw.begin() + p * K + r.nkf, r.common_words);
-  }
+  R.unpack();
   return ORBPL_OK;
 }
 

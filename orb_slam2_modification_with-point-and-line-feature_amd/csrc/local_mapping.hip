@@ -40,6 +40,7 @@
 #include "block_ops.h"
 #include "localmap_core.h"
 #include "match_common.h"
+#include "host_rows.h"
 #include "host_stage.h"
 #include "orbpl_runtime.h"
 
@@ -524,9 +525,6 @@ using namespace orbpl;
 
 namespace {
 
-// what of a keyframe a call reads
-enum { kReadPoints = 1, kReadLines = 2, kReadMapPoints = 4 };
-
 int check_keyframe(const orblm_keyframe& k, int nlevels, int reads) {
   if (!k.Tcw) return arg_fail("NULL keyframe pose");
   if (reads & kReadPoints) {
@@ -547,94 +545,43 @@ int check_keyframe(const orblm_keyframe& k, int nlevels, int reads) {
   return ORBPL_OK;
 }
 
-// the pool of a host call: every keyframe of every problem, current first
-struct HostPool {
-  std::vector<const orblm_keyframe*> kfs;
-  std::vector<int32_t> cur, neigh;
-  int pitch = 1, lpitch = 1, reads = kReadPoints | kReadLines | kReadMapPoints;
+// the pool of a host call (LmRows) with its staging
+struct HostPool : LmRows {
   HostStage st;
   orblm_device_batch b{};
 
-  // stages the pool and the outputs of nprob problems into b; returns st.rc()
-  int upload(int nprob) {
-    const size_t K = kfs.size(), P = (size_t)pitch, LP = (size_t)lpitch;
-    std::vector<int32_t> hid(K), hn(K, 0), hnl(K, 0), hnode(K * P, -1);
-    std::vector<float> hT(K * 16), hur(K * P, -1.0f), hdep(K * P, -1.0f), hmpx(K * P * 3, 0.0f);
-    std::vector<orbpl_keypoint> hk(K * P), hu(K * P);
-    std::vector<uint8_t> hdesc(K * P * 32), hh(K * P, 1), hld(K * LP * 32);
-    std::vector<orbpl_keyline> hkl(K * LP);
-    std::vector<double> hlc(K * LP * 3, 0.0);
-    for (size_t k = 0; k < K; k++) {
-      const orblm_keyframe& f = *kfs[k];
-      hid[k] = f.id;
-      memcpy(&hT[k * 16], f.Tcw, 64);
-      if ((reads & kReadPoints) && f.n) {
-        hn[k] = f.n;
-        memcpy(&hk[k * P], f.kps, (size_t)f.n * sizeof(orbpl_keypoint));
-        memcpy(&hu[k * P], f.kps_un, (size_t)f.n * sizeof(orbpl_keypoint));
-        memcpy(&hur[k * P], f.uright, (size_t)f.n * 4);
-        memcpy(&hdep[k * P], f.depth, (size_t)f.n * 4);
-        memcpy(&hdesc[k * P * 32], f.desc, (size_t)f.n * 32);
-        memcpy(&hnode[k * P], f.feat_node, (size_t)f.n * 4);
-        memcpy(&hh[k * P], f.has_mp, (size_t)f.n);
-        if (reads & kReadMapPoints) memcpy(&hmpx[k * P * 3], f.mp_xyz, (size_t)f.n * 12);
-      }
-      if ((reads & kReadLines) && f.nl) {
-        hnl[k] = f.nl;
-        memcpy(&hkl[k * LP], f.klines, (size_t)f.nl * sizeof(orbpl_keyline));
-        memcpy(&hld[k * LP * 32], f.ldesc, (size_t)f.nl * 32);
-        memcpy(&hlc[k * LP * 3], f.lcoef, (size_t)f.nl * 24);
-      }
-    }
-    const size_t N = (size_t)nprob;
-    b.nkf = (int)K;
+  // packs and stages the pool and the outputs of its problems into b; returns st.rc()
+  int upload() {
+    pack();
+    b.nkf = (int)kfs.size();
     b.kp_pitch = pitch;
     b.line_pitch = lpitch;
-    b.d_kf_id = st.in(hid);
-    b.d_kf_n = st.in(hn);
-    b.d_kf_Tcw = st.in(hT);
-    b.d_kps = st.in(hk);
-    b.d_kps_un = st.in(hu);
-    b.d_uright = st.in(hur);
-    b.d_depth = st.in(hdep);
-    b.d_desc = st.in(hdesc);
-    b.d_feat_node = st.in(hnode);
-    b.d_has_mp = st.in(hh);
-    b.d_mp_xyz = st.in(hmpx);
-    b.d_kf_nl = st.in(hnl);
-    b.d_klines = st.in(hkl);
-    b.d_ldesc = st.in(hld);
-    b.d_lcoef = st.in(hlc);
+    b.d_kf_id = st.in(id);
+    b.d_kf_n = st.in(n);
+    b.d_kf_Tcw = st.in(Tcw);
+    b.d_kps = st.in(kps);
+    b.d_kps_un = st.in(kps_un);
+    b.d_uright = st.in(uright);
+    b.d_depth = st.in(depth);
+    b.d_desc = st.in(desc);
+    b.d_feat_node = st.in(feat_node);
+    b.d_has_mp = st.in(has_mp);
+    b.d_mp_xyz = st.in(mp_xyz);
+    b.d_kf_nl = st.in(nl);
+    b.d_klines = st.in(klines);
+    b.d_ldesc = st.in(ldesc);
+    b.d_lcoef = st.in(lcoef);
     b.d_cur = st.in(cur);
     b.d_neigh = st.in(neigh);
-    b.d_points = st.out<orblm_point_record>(N * P);
-    b.d_n_points = st.out<int32_t>(N);
-    b.d_kf1_point_record = st.out<int32_t>(N * P);
-    b.d_pairs = st.out<int32_t>(N * lm::kNeighbours);
-    b.d_lines = st.out<orblm_line_record>(N * lm::kNeighbours * LP);
-    b.d_n_lines = st.out<int32_t>(N);
-    b.d_kf1_line_record = st.out<int32_t>(N * LP);
-    b.d_line_pairs = st.out<int32_t>(N * lm::kNeighbours);
+    b.d_points = st.out(points);
+    b.d_n_points = st.out(n_points);
+    b.d_kf1_point_record = st.out(point_record);
+    b.d_pairs = st.out(pairs);
+    b.d_lines = st.out(lines);
+    b.d_n_lines = st.out(n_lines);
+    b.d_kf1_line_record = st.out(line_record);
+    b.d_line_pairs = st.out(line_pairs);
     return st.rc();
-  }
-
-  void add_keyframe(const orblm_keyframe* k) {
-    kfs.push_back(k);
-    if (reads & kReadPoints) pitch = std::max(pitch, k->n);
-    if (reads & kReadLines) lpitch = std::max(lpitch, k->nl);
-  }
-
-  void add_problem(const orblm_keyframe* c, const orblm_keyframe* nb, int nn) {
-    cur.push_back((int32_t)kfs.size());
-    add_keyframe(c);
-    for (int k = 0; k < lm::kNeighbours; k++) {
-      if (k < nn) {
-        neigh.push_back((int32_t)kfs.size());
-        add_keyframe(nb + k);
-      } else {
-        neigh.push_back(-1);
-      }
-    }
   }
 };
 
@@ -682,39 +629,13 @@ int orblm_create_new_map_features(const orbpl_camera* cam, const float* scale_fa
     H.add_problem(&r.cur, r.neigh, r.n_neigh);
   }
   if (n == 0) return ORBPL_OK;
-  if ((rc = H.upload(n))) return rc;
+  if ((rc = H.upload())) return rc;
   a.b = H.b;
   launch(a, n, nullptr);   // host-pointer APIs use the null stream
   H.st.launched();
-  const size_t P = (size_t)H.pitch, LP = (size_t)H.lpitch, NB = lm::kNeighbours;
-  std::vector<int32_t> hn(n), hpairs((size_t)n * NB), hrec((size_t)n * P), hnl(n),
-      hlpairs((size_t)n * NB), hlrec((size_t)n * LP);
-  std::vector<orblm_point_record> hp((size_t)n * P);
-  std::vector<orblm_line_record> hl((size_t)n * NB * LP);
-  H.st.back(hn, H.b.d_n_points);
-  H.st.back(hpairs, H.b.d_pairs);
-  H.st.back(hrec, H.b.d_kf1_point_record);
-  H.st.back(hp, H.b.d_points);
-  H.st.back(hnl, H.b.d_n_lines);
-  H.st.back(hlpairs, H.b.d_line_pairs);
-  H.st.back(hlrec, H.b.d_kf1_line_record);
-  H.st.back(hl, H.b.d_lines);
+  H.st.back_outs();
   if (H.st.rc()) return H.st.rc();
-  for (int p = 0; p < n; p++) {
-    orblm_problem& r = problems[p];
-    r.n_points = hn[p];
-    r.n_lines = hnl[p];
-    std::copy(hpairs.begin() + p * NB, hpairs.begin() + (p + 1) * NB, r.pairs);
-    std::copy(hlpairs.begin() + p * NB, hlpairs.begin() + (p + 1) * NB, r.line_pairs);
-    if (r.cur.n > 0) {
-      std::copy(hrec.begin() + p * P, hrec.begin() + p * P + r.cur.n, r.kf1_point_record);
-      std::copy(hp.begin() + p * P, hp.begin() + p * P + hn[p], r.points);
-    }
-    if (r.cur.nl > 0) {
-      std::copy(hlrec.begin() + p * LP, hlrec.begin() + p * LP + r.cur.nl, r.kf1_line_record);
-      std::copy(hl.begin() + p * NB * LP, hl.begin() + p * NB * LP + hnl[p], r.lines);
-    }
-  }
+  H.unpack(problems);
   return ORBPL_OK;
 }
 
@@ -733,7 +654,7 @@ int orbm_search_for_triangulation(const orbpl_camera* cam, const float* scale_fa
     return rc;
   if (kf1->n > 0 && !pairs) return arg_fail("NULL pairs");
   H.add_problem(kf1, kf2, 1);
-  H.upload(1);
+  H.upload();
   a.b = H.b;
   a.match_only = 1;
   a.only_stereo = only_stereo != 0;
@@ -747,10 +668,9 @@ int orbm_search_for_triangulation(const orbpl_camera* cam, const float* scale_fa
   if (H.st.rc()) return H.st.rc();
   launch(a, 1, nullptr);
   H.st.launched();
-  int32_t hpairs[lm::kNeighbours];
-  H.st.back(hpairs, H.b.d_pairs, lm::kNeighbours);
+  H.st.back(H.pairs);
   if (H.st.rc()) return H.st.rc();
-  *npairs = std::max(hpairs[0], 0);
+  *npairs = std::max(H.pairs.at(0), 0);
   H.st.back(pairs, a.pairs_out, 2 * (size_t)*npairs);
   if (f12_out) H.st.back(f12_out, a.f12_out, 9);
   return H.st.rc();
@@ -778,17 +698,16 @@ int orbl_search_for_triangulation(int nl1, const uint8_t* ldesc1, int nl2, const
   HostPool H;
   H.reads = kReadLines;
   H.add_problem(&k1, &k2, 1);
-  H.upload(1);
+  H.upload();
   a.b = H.b;
   a.match_only = 2;
   a.pairs_out = H.st.out<int32_t>(2 * (size_t)H.lpitch);
   if (H.st.rc()) return H.st.rc();
   launch(a, 1, nullptr);
   H.st.launched();
-  int32_t hpairs[lm::kNeighbours];
-  H.st.back(hpairs, H.b.d_line_pairs, lm::kNeighbours);
+  H.st.back(H.line_pairs);
   if (H.st.rc()) return H.st.rc();
-  *npairs = std::max(hpairs[0], 0);
+  *npairs = std::max(H.line_pairs.at(0), 0);
   H.st.back(pairs, a.pairs_out, 2 * (size_t)*npairs);
   return H.st.rc();
 }

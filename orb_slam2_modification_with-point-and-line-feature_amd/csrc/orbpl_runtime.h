@@ -1,6 +1,9 @@
 // Internal runtime helpers shared by the C-ABI translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
+
+#include <cmath>
 
 #include "orb_kernels.h"
 
@@ -9,6 +12,12 @@ struct orbx_ctx;
 namespace orbpl {
 int hip_fail(hipError_t e, const char* what, int line);
 int arg_fail(const char* msg);
+// SetRansacParameters' ceil(log(1 - p) / log(1 - eps^3)) as the reference's int:
+// a value that is not finite or not an int is INT_MIN, x86's conversion
+inline int ransac_iterations(double probability, float eps) {
+  const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow(eps, 3)));
+  return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN;
+}
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device):
 // HIP function attributes are per device, so a process-wide flag would skip
 // the second device. Thread-safe; the current device is hipGetDevice's.

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/orbpl.h"
+#include "host_rows.h"
 #include "host_stage.h"
 #include "orbpl_runtime.h"
 #include "pnp_core.h"
@@ -305,14 +306,7 @@ int orbpnp_ransac_parameters(int n, double probability, int min_inliers, int max
   if (nMinInliers < min_set) nMinInliers = min_set;
   float eps = epsilon;
   if (eps < (float)nMinInliers / n) eps = (float)nMinInliers / n;
-  int nIterations;
-  if (nMinInliers == n) {
-    nIterations = 1;
-  } else {
-    // a value that is not finite or not an int is INT_MIN, x86's conversion
-    const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow(eps, 3)));
-    nIterations = (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN;
-  }
+  const int nIterations = nMinInliers == n ? 1 : ransac_iterations(probability, eps);
   *out_min_inliers = nMinInliers;
   *out_max_its = std::max(1, std::min(nIterations, max_iterations));
   *out_epsilon = eps;
@@ -344,6 +338,7 @@ int orbpnp_iterate(const orbpnp_problem* P, int nsolvers, int n_iterations) {
   if (nsolvers < 0 || (nsolvers > 0 && !P)) return arg_fail("bad argument");
   if (nsolvers == 0) return ORBPL_OK;
   size_t ptp = 1, drp = 4;
+  std::vector<size_t> nd(nsolvers);   // the draws a problem can consume
   for (int p = 0; p < nsolvers; p++) {
     const orbpnp_problem& r = P[p];
     if (r.n < 0 || r.n > kPnpMaxPoints) return arg_fail("more than 2048 correspondences");
@@ -359,88 +354,38 @@ int orbpnp_iterate(const orbpnp_problem* P, int nsolvers, int n_iterations) {
     if (r.n_draws < 0 || r.n_draws < 4 * H || (r.n_draws > 0 && !r.draws))
       return arg_fail("fewer draws than 4 per hypothesis");
     ptp = std::max(ptp, (size_t)r.n);
-    drp = std::max(drp, (size_t)(4 * H));
+    drp = std::max(drp, nd[p] = (size_t)(4 * H));
   }
-  const size_t S = nsolvers;
-  std::vector<int> h_n(S), h_min(S), h_max(S), h_dr(S * drp, 0), h_it(S), h_best(S);
-  std::vector<float> h_cam(S * 4), h_p2(S * ptp * 2, 0.0f), h_p3(S * ptp * 3, 0.0f),
-      h_me(S * ptp, 0.0f), h_bT(S * 16);
-  std::vector<uint8_t> h_bm(S * ptp, 0);
-  for (size_t p = 0; p < S; p++) {
-    const orbpnp_problem& r = P[p];
-    const long long H = pnp_hypotheses(r.n, r.min_inliers, r.max_its, *r.iterations, n_iterations);
-    h_n[p] = r.n;
-    h_min[p] = r.min_inliers;
-    h_max[p] = r.max_its;
-    h_it[p] = *r.iterations;
-    h_best[p] = *r.best_inliers;
-    h_cam[4 * p] = r.fx;
-    h_cam[4 * p + 1] = r.fy;
-    h_cam[4 * p + 2] = r.cx;
-    h_cam[4 * p + 3] = r.cy;
-    std::copy(r.best_Tcw, r.best_Tcw + 16, h_bT.begin() + 16 * p);
-    std::copy(r.draws, r.draws + 4 * H, h_dr.begin() + p * drp);
-    if (!r.n) continue;
-    std::copy(r.p2d, r.p2d + 2 * r.n, h_p2.begin() + p * ptp * 2);
-    std::copy(r.p3d, r.p3d + 3 * r.n, h_p3.begin() + p * ptp * 3);
-    std::copy(r.max_error, r.max_error + r.n, h_me.begin() + p * ptp);
-    std::copy(r.best_mask, r.best_mask + r.n, h_bm.begin() + p * ptp);
-  }
+  PnpRows R(P, nsolvers, ptp, drp, nd);
   HostStage st;
-  PnpArgs a{st.in(h_n),
-            st.in(h_cam),
-            st.in(h_p2),
-            st.in(h_p3),
-            st.in(h_me),
+  PnpArgs a{st.in(R.n),
+            st.in(R.cam),
+            st.in(R.p2d),
+            st.in(R.p3d),
+            st.in(R.max_error),
             (int)ptp,
-            st.in(h_min),
-            st.in(h_max),
-            st.in(h_dr),
+            st.in(R.min_inliers),
+            st.in(R.max_its),
+            st.in(R.draws),
             (int)drp,
             (double)RAND_MAX + 1.0,
             n_iterations,
-            st.in(h_it),
-            st.in(h_best),
-            st.in(h_bm),
-            st.in(h_bT),
-            st.out<float>(S * 16),
-            st.out<int>(S),
-            st.out<int>(S),
-            st.out<int>(S),
-            st.out<uint8_t>(S * ptp),
-            st.out<int>(S)};
+            st.inout(R.iterations),
+            st.inout(R.best_inliers),
+            st.inout(R.best_mask),
+            st.inout(R.best_Tcw),
+            st.out(R.Tcw),
+            st.out(R.result),
+            st.out(R.no_more),
+            st.out(R.n_inliers),
+            st.out(R.inliers),
+            st.out(R.draws_consumed)};
   if (st.rc()) return st.rc();
   launch_pnp_iterate(a, nsolvers, nullptr);   // host-pointer APIs use the null stream
   st.launched();
-  std::vector<int> h_res(S), h_nm(S), h_ni(S), h_dc(S);
-  std::vector<float> h_T(S * 16);
-  std::vector<uint8_t> h_inl(S * ptp);
-  st.back(h_res, a.result);
-  st.back(h_nm, a.no_more);
-  st.back(h_ni, a.n_inliers);
-  st.back(h_dc, a.draws_consumed);
-  st.back(h_T, a.Tcw);
-  st.back(h_inl, a.inliers);
-  st.back(h_it, a.iterations);
-  st.back(h_best, a.best_count);
-  st.back(h_bT, a.best_Tcw);
-  st.back(h_bm, a.best_mask);
+  st.back_outs();
   if (st.rc()) return st.rc();
-  for (size_t p = 0; p < S; p++) {
-    const orbpnp_problem& r = P[p];
-    *r.iterations = h_it[p];
-    *r.best_inliers = h_best[p];
-    *r.result = h_res[p];
-    *r.no_more = h_nm[p];
-    *r.n_inliers = h_ni[p];
-    *r.draws_consumed = h_dc[p];
-    std::copy(h_T.begin() + 16 * p, h_T.begin() + 16 * p + 16, r.Tcw);
-    if (r.n >= r.min_inliers) {  // the early return leaves the state as it was
-      std::copy(h_bT.begin() + 16 * p, h_bT.begin() + 16 * p + 16, r.best_Tcw);
-      std::copy(h_bm.begin() + p * ptp, h_bm.begin() + p * ptp + r.n, r.best_mask);
-    }
-    if (r.n) std::copy(h_inl.begin() + p * ptp, h_inl.begin() + p * ptp + r.n, r.inliers);
-  }
+  R.unpack();
   return ORBPL_OK;
 }
 

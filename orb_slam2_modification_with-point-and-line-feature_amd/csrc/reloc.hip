@@ -22,6 +22,7 @@
 
 #include "../../include/orbpl.h"
 #include "block_ops.h"
+#include "host_rows.h"
 #include "host_stage.h"
 #include "orbpl_runtime.h"
 #include "reloc_kernels.h"
@@ -433,6 +434,16 @@ T* upload(Grow& g, const std::vector<T>& h, hipError_t* e) {
   return g.as<T>();
 }
 
+// a column's size, and the whole of it back from its device array
+template <class T>
+size_t bytes(const Rows<T>& c) {
+  return c.h.size() * sizeof(T);
+}
+template <class T>
+hipError_t download(Rows<T>& c, const T* d) {
+  return hipMemcpy(c.h.data(), d, bytes(c), hipMemcpyDeviceToHost);
+}
+
 constexpr int kNumIn = 28, kNumPair = 52, kNumProb = 16;
 
 }  // namespace
@@ -758,167 +769,77 @@ int orbrl_relocalize(orbrl_handle* h, orbrl_problem* probs, int n, int scoring) 
   if (!h || n < 0 || (n > 0 && !probs)) return arg_fail("bad argument");
   if (n > h->max_problems) return arg_fail("more problems than the handle was created for");
   if (n == 0) return ORBPL_OK;
-  const size_t P = h->kp_pitch, K = kKfdbMaxKf, NP = n;
-  size_t entp = 1, qp = 1, nslots = 0, sp = 1;
-  std::vector<int> kf_first(NP);
+  const size_t P = h->kp_pitch, NP = n;
+  size_t entp = 1, qp = 1, sp = 1;
   for (int p = 0; p < n; p++) {
     const orbrl_problem& r = probs[p];
-    if (r.nkf < 0 || r.nkf > kKfdbMaxKf) return arg_fail("more than 64 keyframes in a database");
-    if (r.nq_words < 0 || r.nq_words > kKfdbMaxWords)
-      return arg_fail("more than 4096 entries in the query's BowVector");
+    if (const char* no = kfdb_refusal(r, "offsets must start at 0", &entp, &qp)) return arg_fail(no);
     if (r.n < 0 || r.n > (int)P) return arg_fail("more keypoints than kp_pitch");
     if (r.n > 0 && (!r.kps_un || !r.uright || !r.desc || !r.feat_node || !r.mp_kf_feature ||
                     !r.outlier))
       return arg_fail("NULL frame arrays");
     if (!r.records) return arg_fail("NULL output");
-    if (r.nq_words > 0 && (!r.q_words || !r.q_vals)) return arg_fail("NULL query BowVector");
     if (r.n_draw_streams < 0 || r.n_draw_streams > kKfdbMaxKf || (r.n_draw_streams > 0 && !r.draws))
       return arg_fail("bad draw streams");
-    if (r.nkf > 0) {
-      if (!r.kf_off || !r.covis || !r.reloc_score || !r.kf_feat_off)
-        return arg_fail("NULL keyframe arrays");
-      if (r.kf_off[0] != 0 || r.kf_feat_off[0] != 0) return arg_fail("offsets must start at 0");
-      for (int k = 0; k < r.nkf; k++) {
-        const int len = r.kf_off[k + 1] - r.kf_off[k];
-        if (len < 0 || len > kKfdbMaxWords)
-          return arg_fail("a keyframe's BowVector has a negative length or more than 4096 entries");
-        const int nf = r.kf_feat_off[k + 1] - r.kf_feat_off[k];
-        if (nf < 0 || nf > (int)P) return arg_fail("a keyframe has more features than kp_pitch");
-      }
-      if (r.kf_off[r.nkf] > 0 && (!r.kf_words || !r.kf_vals))
-        return arg_fail("NULL keyframe BowVectors");
-      if (r.kf_feat_off[r.nkf] > 0 &&
-          (!r.kf_angle || !r.kf_feat_node || !r.kf_desc || !r.kf_valid || !r.mp_xyz ||
-           !r.mp_min_dist || !r.mp_max_dist || !r.mp_desc))
-        return arg_fail("NULL keyframe feature arrays");
-      entp = std::max(entp, (size_t)r.kf_off[r.nkf]);
-    }
-    qp = std::max(qp, (size_t)r.nq_words);
     sp = std::max(sp, (size_t)r.n_draw_streams);
-    kf_first[p] = (int)nslots;
-    nslots += r.nkf;
-  }
-  const size_t S = std::max<size_t>(1, nslots), DP = h->draw_pitch;
-  // ---- pack ----
-  std::vector<int> h_nkf(NP), h_off(NP * (K + 1), 0), h_cov(NP * K * kKfdbCovis, -1), h_qn(NP),
-      h_n(NP), h_fnode(NP * P, -1), h_kfn(S, 0), h_kfnode(S * P, -1), h_draws(NP * sp * DP, 0),
-      h_ns(NP);
-  std::vector<uint32_t> h_kw(NP * entp, 0), h_qw(NP * qp, 0);
-  std::vector<double> h_kv(NP * entp, 0), h_qv(NP * qp, 0);
-  std::vector<float> h_rs(NP * K, 0.0f), h_ur(NP * P, -1.0f), h_kang(S * P, 0.0f),
-      h_xyz(S * P * 3, 0.0f), h_mn(S * P, 0.0f), h_mx(S * P, 0.0f);
-  std::vector<KeyPointD> h_kps(NP * P);
-  std::vector<uint8_t> h_desc(NP * P * 32, 0), h_kdesc(S * P * 32, 0), h_kval(S * P, 0),
-      h_mdesc(S * P * 32, 0);
-  for (size_t p = 0; p < NP; p++) {
-    const orbrl_problem& r = probs[p];
-    h_nkf[p] = r.nkf;
-    h_qn[p] = r.nq_words;
-    h_n[p] = r.n;
-    h_ns[p] = r.n_draw_streams;
-    std::copy(r.q_words, r.q_words + r.nq_words, h_qw.begin() + p * qp);
-    std::copy(r.q_vals, r.q_vals + r.nq_words, h_qv.begin() + p * qp);
-    if (r.n) {
-      const KeyPointD* kp = reinterpret_cast<const KeyPointD*>(r.kps_un);
-      std::copy(kp, kp + r.n, h_kps.begin() + p * P);
-      std::copy(r.uright, r.uright + r.n, h_ur.begin() + p * P);
-      std::copy(r.desc, r.desc + (size_t)r.n * 32, h_desc.begin() + p * P * 32);
-      std::copy(r.feat_node, r.feat_node + r.n, h_fnode.begin() + p * P);
-    }
-    if (r.n_draw_streams)
-      std::copy(r.draws, r.draws + (size_t)r.n_draw_streams * DP, h_draws.begin() + p * sp * DP);
     if (!r.nkf) continue;
-    std::copy(r.kf_off, r.kf_off + r.nkf + 1, h_off.begin() + p * (K + 1));
-    const int ne = r.kf_off[r.nkf];
-    std::copy(r.kf_words, r.kf_words + ne, h_kw.begin() + p * entp);
-    std::copy(r.kf_vals, r.kf_vals + ne, h_kv.begin() + p * entp);
-    std::copy(r.covis, r.covis + r.nkf * kKfdbCovis, h_cov.begin() + p * K * kKfdbCovis);
-    std::copy(r.reloc_score, r.reloc_score + r.nkf, h_rs.begin() + p * K);
+    if (!r.kf_feat_off) return arg_fail("NULL keyframe arrays");
+    if (r.kf_feat_off[0] != 0) return arg_fail("offsets must start at 0");
     for (int k = 0; k < r.nkf; k++) {
-      const size_t b = r.kf_feat_off[k], nf = r.kf_feat_off[k + 1] - b, sb = (kf_first[p] + k) * P;
-      h_kfn[kf_first[p] + k] = (int)nf;
-      if (!nf) continue;
-      std::copy(r.kf_angle + b, r.kf_angle + b + nf, h_kang.begin() + sb);
-      std::copy(r.kf_feat_node + b, r.kf_feat_node + b + nf, h_kfnode.begin() + sb);
-      std::copy(r.kf_desc + b * 32, r.kf_desc + (b + nf) * 32, h_kdesc.begin() + sb * 32);
-      std::copy(r.kf_valid + b, r.kf_valid + b + nf, h_kval.begin() + sb);
-      std::copy(r.mp_xyz + b * 3, r.mp_xyz + (b + nf) * 3, h_xyz.begin() + sb * 3);
-      std::copy(r.mp_min_dist + b, r.mp_min_dist + b + nf, h_mn.begin() + sb);
-      std::copy(r.mp_max_dist + b, r.mp_max_dist + b + nf, h_mx.begin() + sb);
-      std::copy(r.mp_desc + b * 32, r.mp_desc + (b + nf) * 32, h_mdesc.begin() + sb * 32);
+      const int nf = r.kf_feat_off[k + 1] - r.kf_feat_off[k];
+      if (nf < 0 || nf > (int)P) return arg_fail("a keyframe has more features than kp_pitch");
     }
+    if (r.kf_feat_off[r.nkf] > 0 &&
+        (!r.kf_angle || !r.kf_feat_node || !r.kf_desc || !r.kf_valid || !r.mp_xyz ||
+         !r.mp_min_dist || !r.mp_max_dist || !r.mp_desc))
+      return arg_fail("NULL keyframe feature arrays");
   }
+  RelocRows R(probs, NP, P, h->draw_pitch, entp, qp, sp);
   Grow* g = h->in;
   int gi = 0;
   hipError_t e = hipSuccess;
-  auto* d_nkf = upload(g[gi++], h_nkf, &e);
-  auto* d_off = upload(g[gi++], h_off, &e);
-  auto* d_cov = upload(g[gi++], h_cov, &e);
-  auto* d_qn = upload(g[gi++], h_qn, &e);
-  auto* d_n = upload(g[gi++], h_n, &e);
-  auto* d_fnode = upload(g[gi++], h_fnode, &e);
-  auto* d_kfn = upload(g[gi++], h_kfn, &e);
-  auto* d_kfnode = upload(g[gi++], h_kfnode, &e);
-  auto* d_draws = upload(g[gi++], h_draws, &e);
-  auto* d_ns = upload(g[gi++], h_ns, &e);
-  auto* d_kw = upload(g[gi++], h_kw, &e);
-  auto* d_qw = upload(g[gi++], h_qw, &e);
-  auto* d_kv = upload(g[gi++], h_kv, &e);
-  auto* d_qv = upload(g[gi++], h_qv, &e);
-  auto* d_rs = upload(g[gi++], h_rs, &e);
-  auto* d_ur = upload(g[gi++], h_ur, &e);
-  auto* d_kang = upload(g[gi++], h_kang, &e);
-  auto* d_xyz = upload(g[gi++], h_xyz, &e);
-  auto* d_mn = upload(g[gi++], h_mn, &e);
-  auto* d_mx = upload(g[gi++], h_mx, &e);
-  auto* d_kps = upload(g[gi++], h_kps, &e);
-  auto* d_desc = upload(g[gi++], h_desc, &e);
-  auto* d_kdesc = upload(g[gi++], h_kdesc, &e);
-  auto* d_kval = upload(g[gi++], h_kval, &e);
-  auto* d_mdesc = upload(g[gi++], h_mdesc, &e);
-  auto* d_first = upload(g[gi++], kf_first, &e);
+  orbrl_device_batch b{};
+  b.d_nkf = upload(g[gi++], R.db.nkf.h, &e);
+  b.d_kf_off = upload(g[gi++], R.db.kf_off.h, &e);
+  b.d_covis = upload(g[gi++], R.db.covis.h, &e);
+  b.d_q_n = upload(g[gi++], R.db.q_n.h, &e);
+  b.d_n = upload(g[gi++], R.n.h, &e);
+  b.d_feat_node = upload(g[gi++], R.feat_node.h, &e);
+  b.d_kf_n = upload(g[gi++], R.kf_n.h, &e);
+  b.d_kf_feat_node = upload(g[gi++], R.kf_feat_node.h, &e);
+  b.d_draws = upload(g[gi++], R.draws.h, &e);
+  b.d_n_streams = upload(g[gi++], R.n_streams.h, &e);
+  b.d_kf_words = upload(g[gi++], R.db.kf_words.h, &e);
+  b.d_q_words = upload(g[gi++], R.db.q_words.h, &e);
+  b.d_kf_vals = upload(g[gi++], R.db.kf_vals.h, &e);
+  b.d_q_vals = upload(g[gi++], R.db.q_vals.h, &e);
+  b.d_reloc_score = upload(g[gi++], R.db.reloc_score.h, &e);
+  b.d_uright = upload(g[gi++], R.uright.h, &e);
+  b.d_kf_angle = upload(g[gi++], R.kf_angle.h, &e);
+  b.d_mp_xyz = upload(g[gi++], R.mp_xyz.h, &e);
+  b.d_mp_min_dist = upload(g[gi++], R.mp_min_dist.h, &e);
+  b.d_mp_max_dist = upload(g[gi++], R.mp_max_dist.h, &e);
+  b.d_kps_un = upload(g[gi++], R.kps_un.h, &e);
+  b.d_desc = upload(g[gi++], R.desc.h, &e);
+  b.d_kf_desc = upload(g[gi++], R.kf_desc.h, &e);
+  b.d_kf_valid = upload(g[gi++], R.kf_valid.h, &e);
+  b.d_mp_desc = upload(g[gi++], R.mp_desc.h, &e);
+  b.d_kf_first = upload(g[gi++], R.kf_first.h, &e);
   HIP_CHECK(e);
   Grow& g_cand = g[gi++];
   Grow& g_nc = g[gi++];
   static_assert(kNumIn == 28, "one Grow per input array");
-  HIP_CHECK(g_cand.need(NP * K * 4));
-  HIP_CHECK(g_nc.need(NP * 4));
+  HIP_CHECK(g_cand.need(bytes(R.cand)));
+  HIP_CHECK(g_nc.need(bytes(R.ncand)));
   // ---- per-problem outputs ----
   Grow* o = h->prob + 7;
-  HIP_CHECK(o[0].need(NP * 4 * 6));
-  HIP_CHECK(o[1].need(NP * 64));
-  HIP_CHECK(o[2].need(NP * P * 4));
-  HIP_CHECK(o[3].need(NP * P));
-  HIP_CHECK(o[4].need(NP * K * kRelocRec * 4));
-  orbrl_device_batch b{};
-  b.d_nkf = d_nkf;
-  b.d_kf_off = d_off;
-  b.d_kf_words = d_kw;
-  b.d_kf_vals = d_kv;
+  HIP_CHECK(o[0].need(bytes(R.scalars)));
+  HIP_CHECK(o[1].need(bytes(R.Tcw)));
+  HIP_CHECK(o[2].need(bytes(R.mp_kf_feature)));
+  HIP_CHECK(o[3].need(bytes(R.outlier)));
+  HIP_CHECK(o[4].need(bytes(R.records)));
   b.ent_pitch = (int64_t)entp;
-  b.d_covis = d_cov;
-  b.d_reloc_score = d_rs;
-  b.d_q_n = d_qn;
-  b.d_q_words = d_qw;
-  b.d_q_vals = d_qv;
   b.q_pitch = (int64_t)qp;
-  b.d_kf_first = d_first;
-  b.d_kf_n = d_kfn;
-  b.d_kf_angle = d_kang;
-  b.d_kf_feat_node = d_kfnode;
-  b.d_kf_desc = d_kdesc;
-  b.d_kf_valid = d_kval;
-  b.d_mp_xyz = d_xyz;
-  b.d_mp_min_dist = d_mn;
-  b.d_mp_max_dist = d_mx;
-  b.d_mp_desc = d_mdesc;
-  b.d_n = d_n;
-  b.d_kps_un = reinterpret_cast<const orbpl_keypoint*>(d_kps);
-  b.d_uright = d_ur;
-  b.d_desc = d_desc;
-  b.d_feat_node = d_fnode;
-  b.d_draws = d_draws;
-  b.d_n_streams = d_ns;
   b.stream_pitch = (int32_t)sp;
   b.d_cand = g_cand.as<int32_t>();
   b.d_ncand = g_nc.as<int32_t>();
@@ -934,38 +855,15 @@ int orbrl_relocalize(orbrl_handle* h, orbrl_problem* probs, int n, int scoring) 
   b.d_records = o[4].as<int32_t>();
   const int rc = orbrl_relocalize_batch_device(h, &b, n, scoring, nullptr);   // the null stream
   if (rc) return rc;
-  // ---- unpack ----
-  std::vector<int> h_sc(NP * 6), h_cand(NP * K), h_nc(NP), h_om(NP * P), h_rec(NP * K * kRelocRec);
-  std::vector<float> h_T(NP * 16);
-  std::vector<uint8_t> h_oo(NP * P);
-  HIP_CHECK(hipMemcpy(h_sc.data(), b.d_ok, NP * 24, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_cand.data(), b.d_cand, NP * K * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_nc.data(), b.d_ncand, NP * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_om.data(), b.d_mp_kf_feature, NP * P * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_oo.data(), b.d_outlier, NP * P, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_rec.data(), b.d_records, NP * K * kRelocRec * 4, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_T.data(), b.d_Tcw, NP * 64, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(h_rs.data(), b.d_reloc_score, NP * K * 4, hipMemcpyDeviceToHost));
-  bool exhausted = false;
-  for (size_t p = 0; p < NP; p++) {
-    orbrl_problem& r = probs[p];
-    r.ok = h_sc[p];
-    r.status = h_sc[NP + p];
-    r.winner = h_sc[2 * NP + p];
-    r.rounds = h_sc[3 * NP + p];
-    r.n_good = h_sc[4 * NP + p];
-    r.n_candidates = h_sc[5 * NP + p];
-    r.ncand = h_nc[p];
-    for (int c = 0; c < kKfdbMaxKf; c++) r.cand[c] = c < h_nc[p] ? h_cand[p * K + c] : -1;
-    std::copy(h_T.begin() + 16 * p, h_T.begin() + 16 * p + 16, r.Tcw);
-    if (r.n) {
-      std::copy(h_om.begin() + p * P, h_om.begin() + p * P + r.n, r.mp_kf_feature);
-      std::copy(h_oo.begin() + p * P, h_oo.begin() + p * P + r.n, r.outlier);
-    }
-    std::copy(h_rec.begin() + p * K * kRelocRec, h_rec.begin() + (p + 1) * K * kRelocRec, r.records);
-    if (r.nkf) std::copy(h_rs.begin() + p * K, h_rs.begin() + p * K + r.nkf, r.reloc_score);
-    exhausted |= r.status == ORBRL_DRAW_EXHAUSTED;
-  }
+  HIP_CHECK(download(R.scalars, b.d_ok));
+  HIP_CHECK(download(R.cand, b.d_cand));
+  HIP_CHECK(download(R.ncand, b.d_ncand));
+  HIP_CHECK(download(R.mp_kf_feature, b.d_mp_kf_feature));
+  HIP_CHECK(download(R.outlier, b.d_outlier));
+  HIP_CHECK(download(R.records, b.d_records));
+  HIP_CHECK(download(R.Tcw, b.d_Tcw));
+  HIP_CHECK(download(R.db.reloc_score, b.d_reloc_score));
+  const bool exhausted = R.unpack();
   return exhausted ? ORBPL_ERR_OVERFLOW : ORBPL_OK;
 }
 

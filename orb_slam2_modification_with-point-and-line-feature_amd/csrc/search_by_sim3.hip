@@ -20,6 +20,7 @@
 
 #include "../../include/orbpl.h"
 #include "block_ops.h"
+#include "host_rows.h"
 #include "host_stage.h"
 #include "lsd_math.h"
 #include "match_common.h"
@@ -249,101 +250,46 @@ int orbm_search_by_sim3(const orbpl_camera* cam, const float* scale_factors, int
     TrackConsts c;
     return make_consts(cam, scale_factors, nullptr, nlevels, &c);
   }
-  const size_t S = npairs;
-  struct Side {
-    std::vector<int> n;
-    std::vector<KeyPointD> kps;
-    std::vector<uint8_t> desc, valid, mp_desc;
-    std::vector<float> xyz, mind, maxd, Tcw;
-    Side(size_t S, size_t pitch)
-        : n(S), kps(S * pitch, KeyPointD{}), desc(S * pitch * 32, 0), valid(S * pitch, 0),
-          mp_desc(S * pitch * 32, 0), xyz(S * pitch * 3, 0.0f), mind(S * pitch, 0.0f),
-          maxd(S * pitch, 0.0f), Tcw(S * 16) {}
-    void put(size_t p, size_t pitch, const orbm_sim3_keyframe& k) {
-      n[p] = k.n;
-      std::copy(k.Tcw, k.Tcw + 16, Tcw.begin() + 16 * p);
-      if (!k.n) return;
-      const size_t o = p * pitch, m = k.n;
-      std::copy(reinterpret_cast<const KeyPointD*>(k.kps_un),
-                reinterpret_cast<const KeyPointD*>(k.kps_un) + m, kps.begin() + o);
-      std::copy(k.desc, k.desc + 32 * m, desc.begin() + 32 * o);
-      std::copy(k.valid, k.valid + m, valid.begin() + o);
-      std::copy(k.mp_desc, k.mp_desc + 32 * m, mp_desc.begin() + 32 * o);
-      std::copy(k.xyz, k.xyz + 3 * m, xyz.begin() + 3 * o);
-      std::copy(k.min_dist, k.min_dist + m, mind.begin() + o);
-      std::copy(k.max_dist, k.max_dist + m, maxd.begin() + o);
-    }
-  };
-  Side a(S, p1), bb(S, p2);
-  std::vector<float> h_s(S), h_R(S * 9), h_t(S * 3);
-  std::vector<int> h_m(S * p1, -1);
-  for (size_t p = 0; p < S; p++) {
-    const orbm_sim3_pair& r = P[p];
-    a.put(p, p1, r.kf1);
-    bb.put(p, p2, r.kf2);
-    h_s[p] = r.s12;
-    std::copy(r.R12, r.R12 + 9, h_R.begin() + 9 * p);
-    std::copy(r.t12, r.t12 + 3, h_t.begin() + 3 * p);
-    if (r.kf1.n) std::copy(r.matched12, r.matched12 + r.kf1.n, h_m.begin() + p * p1);
-  }
+  SbsRows R(P, npairs, p1, p2);
   HostStage st;
   orbm_sim3_device_batch d{};
-  d.d_n1 = st.in(a.n);
-  d.d_n2 = st.in(bb.n);
+  d.d_n1 = st.in(R.k1.n);
+  d.d_n2 = st.in(R.k2.n);
   d.pitch1 = (int)p1;
   d.pitch2 = (int)p2;
-  d.d_kps_un1 = reinterpret_cast<const orbpl_keypoint*>(st.in(a.kps));
-  d.d_desc1 = st.in(a.desc);
-  d.d_valid1 = st.in(a.valid);
-  d.d_xyz1 = st.in(a.xyz);
-  d.d_min_dist1 = st.in(a.mind);
-  d.d_max_dist1 = st.in(a.maxd);
-  d.d_mp_desc1 = st.in(a.mp_desc);
-  d.d_Tcw1 = st.in(a.Tcw);
-  d.d_kps_un2 = reinterpret_cast<const orbpl_keypoint*>(st.in(bb.kps));
-  d.d_desc2 = st.in(bb.desc);
-  d.d_valid2 = st.in(bb.valid);
-  d.d_xyz2 = st.in(bb.xyz);
-  d.d_min_dist2 = st.in(bb.mind);
-  d.d_max_dist2 = st.in(bb.maxd);
-  d.d_mp_desc2 = st.in(bb.mp_desc);
-  d.d_Tcw2 = st.in(bb.Tcw);
-  d.d_s12 = st.in(h_s);
-  d.d_R12 = st.in(h_R);
-  d.d_t12 = st.in(h_t);
-  d.d_matched12 = st.in(h_m);
-  d.d_n_found = st.out<int32_t>(S);
-  d.d_vn_match1 = st.out<int32_t>(S * p1);
-  d.d_vn_match2 = st.out<int32_t>(S * p2);
-  d.d_reason1 = st.out<int32_t>(S * p1);
-  d.d_reason2 = st.out<int32_t>(S * p2);
+  d.d_kps_un1 = st.in(R.k1.kps_un);
+  d.d_desc1 = st.in(R.k1.desc);
+  d.d_valid1 = st.in(R.k1.valid);
+  d.d_xyz1 = st.in(R.k1.xyz);
+  d.d_min_dist1 = st.in(R.k1.min_dist);
+  d.d_max_dist1 = st.in(R.k1.max_dist);
+  d.d_mp_desc1 = st.in(R.k1.mp_desc);
+  d.d_Tcw1 = st.in(R.k1.Tcw);
+  d.d_kps_un2 = st.in(R.k2.kps_un);
+  d.d_desc2 = st.in(R.k2.desc);
+  d.d_valid2 = st.in(R.k2.valid);
+  d.d_xyz2 = st.in(R.k2.xyz);
+  d.d_min_dist2 = st.in(R.k2.min_dist);
+  d.d_max_dist2 = st.in(R.k2.max_dist);
+  d.d_mp_desc2 = st.in(R.k2.mp_desc);
+  d.d_Tcw2 = st.in(R.k2.Tcw);
+  d.d_s12 = st.in(R.s12);
+  d.d_R12 = st.in(R.R12);
+  d.d_t12 = st.in(R.t12);
+  d.d_matched12 = st.inout(R.matched12);
+  d.d_n_found = st.out(R.n_found);
+  d.d_vn_match1 = st.out(R.k1.vn_match);
+  d.d_vn_match2 = st.out(R.k2.vn_match);
+  d.d_reason1 = st.out(R.k1.reason);
+  d.d_reason2 = st.out(R.k2.reason);
   if (st.rc()) return st.rc();
   // the device form refuses the rest (camera, nlevels), launches on the null
   // stream as the host-pointer APIs do and checks the launch
   int rc = orbm_search_by_sim3_batch_device(cam, scale_factors, nlevels, &d, npairs, th, nullptr);
   if (rc) return rc;
-  std::vector<int> h_nf(S), h_v1(S * p1), h_v2(S * p2), h_r1(S * p1), h_r2(S * p2);
-  st.back(h_nf, d.d_n_found);
-  st.back(h_m, d.d_matched12);
-  st.back(h_v1, d.d_vn_match1);
-  st.back(h_v2, d.d_vn_match2);
-  st.back(h_r1, d.d_reason1);
-  st.back(h_r2, d.d_reason2);
+  st.back_outs();
   if (st.rc()) return st.rc();
-  for (size_t p = 0; p < S; p++) {
-    const orbm_sim3_pair& r = P[p];
-    *r.n_found = h_nf[p];
-    const size_t n1 = r.kf1.n, n2 = r.kf2.n;
-    if (n1) {
-      std::copy(h_m.begin() + p * p1, h_m.begin() + p * p1 + n1, r.matched12);
-      std::copy(h_v1.begin() + p * p1, h_v1.begin() + p * p1 + n1, r.vn_match1);
-      std::copy(h_r1.begin() + p * p1, h_r1.begin() + p * p1 + n1, r.reason1);
-    }
-    if (n2) {
-      std::copy(h_v2.begin() + p * p2, h_v2.begin() + p * p2 + n2, r.vn_match2);
-      std::copy(h_r2.begin() + p * p2, h_r2.begin() + p * p2 + n2, r.reason2);
-    }
-  }
+  R.unpack();
   return ORBPL_OK;
 }
 

@@ -28,6 +28,7 @@
 
 #include "../../include/orbpl.h"
 #include "block_ops.h"
+#include "host_rows.h"
 #include "host_stage.h"
 #include "orbpl_runtime.h"
 #include "sim3_core.h"
@@ -234,14 +235,7 @@ int orbsim3_ransac_parameters(int n, double probability, int min_inliers, int ma
   if (n < 0 || !out_max_its) return arg_fail("bad argument");
   // Sim3Solver::SetRansacParameters (:114-138)
   const float epsilon = (float)min_inliers / n;
-  int nIterations;
-  if (min_inliers == n) {
-    nIterations = 1;
-  } else {
-    // a value that is not finite or not an int is INT_MIN, x86's conversion
-    const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow(epsilon, 3)));
-    nIterations = (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN;
-  }
+  const int nIterations = min_inliers == n ? 1 : ransac_iterations(probability, epsilon);
   *out_max_its = std::max(1, std::min(nIterations, max_iterations));
   return ORBPL_OK;
 }
@@ -337,6 +331,7 @@ int orbsim3_iterate(const orbsim3_problem* P, int nsolvers, int n_iterations) {
   if (nsolvers < 0 || (nsolvers > 0 && !P)) return arg_fail("bad argument");
   if (nsolvers == 0) return ORBPL_OK;
   size_t ptp = 1, drp = 3;
+  std::vector<size_t> nd(nsolvers);   // the draws a problem can consume
   for (int p = 0; p < nsolvers; p++) {
     const orbsim3_problem& r = P[p];
     if (r.n < 0 || r.n > kSim3MaxPoints) return arg_fail("more than 2048 correspondences");
@@ -353,110 +348,46 @@ int orbsim3_iterate(const orbsim3_problem* P, int nsolvers, int n_iterations) {
     if (r.n_draws < 0 || r.n_draws < 3 * H || (r.n_draws > 0 && !r.draws))
       return arg_fail("fewer draws than 3 per hypothesis");
     ptp = std::max(ptp, (size_t)r.n);
-    drp = std::max(drp, (size_t)(3 * H));
+    drp = std::max(drp, nd[p] = (size_t)(3 * H));
   }
-  const size_t S = nsolvers;
-  std::vector<int> h_n(S), h_min(S), h_max(S), h_fix(S), h_dr(S * drp, 0), h_it(S), h_best(S),
-      h_m1(S * ptp, 0), h_m2(S * ptp, 0);
-  std::vector<float> h_cam(S * 4), h_X1(S * ptp * 3, 0.0f), h_X2(S * ptp * 3, 0.0f),
-      h_i1(S * ptp * 2, 0.0f), h_i2(S * ptp * 2, 0.0f), h_bT(S * 16), h_bR(S * 9), h_bt(S * 3),
-      h_bs(S);
-  std::vector<uint8_t> h_bm(S * ptp, 0);
-  for (size_t p = 0; p < S; p++) {
-    const orbsim3_problem& r = P[p];
-    const long long H = sim3_hypotheses(r.n, r.min_inliers, r.max_its, *r.iterations, n_iterations);
-    h_n[p] = r.n;
-    h_min[p] = r.min_inliers;
-    h_max[p] = r.max_its;
-    h_fix[p] = r.fix_scale != 0;
-    h_it[p] = *r.iterations;
-    h_best[p] = *r.best_inliers;
-    h_cam[4 * p] = r.fx;
-    h_cam[4 * p + 1] = r.fy;
-    h_cam[4 * p + 2] = r.cx;
-    h_cam[4 * p + 3] = r.cy;
-    std::copy(r.best_T12, r.best_T12 + 16, h_bT.begin() + 16 * p);
-    std::copy(r.best_R, r.best_R + 9, h_bR.begin() + 9 * p);
-    std::copy(r.best_t, r.best_t + 3, h_bt.begin() + 3 * p);
-    h_bs[p] = *r.best_s;
-    if (H) std::copy(r.draws, r.draws + 3 * H, h_dr.begin() + p * drp);
-    if (!r.n) continue;
-    std::copy(r.X3Dc1, r.X3Dc1 + 3 * r.n, h_X1.begin() + p * ptp * 3);
-    std::copy(r.X3Dc2, r.X3Dc2 + 3 * r.n, h_X2.begin() + p * ptp * 3);
-    std::copy(r.P1im1, r.P1im1 + 2 * r.n, h_i1.begin() + p * ptp * 2);
-    std::copy(r.P2im2, r.P2im2 + 2 * r.n, h_i2.begin() + p * ptp * 2);
-    std::copy(r.max_error1, r.max_error1 + r.n, h_m1.begin() + p * ptp);
-    std::copy(r.max_error2, r.max_error2 + r.n, h_m2.begin() + p * ptp);
-    std::copy(r.best_mask, r.best_mask + r.n, h_bm.begin() + p * ptp);
-  }
+  Sim3Rows R(P, nsolvers, ptp, drp, nd);
   HostStage st;
   orbsim3_device_batch a{};
-  a.d_n = st.in(h_n);
-  a.d_cam = st.in(h_cam);
-  a.d_X3Dc1 = st.in(h_X1);
-  a.d_X3Dc2 = st.in(h_X2);
-  a.d_P1im1 = st.in(h_i1);
-  a.d_P2im2 = st.in(h_i2);
-  a.d_max_error1 = st.in(h_m1);
-  a.d_max_error2 = st.in(h_m2);
+  a.d_n = st.in(R.n);
+  a.d_cam = st.in(R.cam);
+  a.d_X3Dc1 = st.in(R.X3Dc1);
+  a.d_X3Dc2 = st.in(R.X3Dc2);
+  a.d_P1im1 = st.in(R.P1im1);
+  a.d_P2im2 = st.in(R.P2im2);
+  a.d_max_error1 = st.in(R.max_error1);
+  a.d_max_error2 = st.in(R.max_error2);
   a.pt_pitch = (int)ptp;
-  a.d_min_inliers = st.in(h_min);
-  a.d_max_its = st.in(h_max);
-  a.d_fix_scale = st.in(h_fix);
-  a.d_draws = st.in(h_dr);
+  a.d_min_inliers = st.in(R.min_inliers);
+  a.d_max_its = st.in(R.max_its);
+  a.d_fix_scale = st.in(R.fix_scale);
+  a.d_draws = st.in(R.draws);
   a.draw_pitch = (int)drp;
-  a.d_iterations = st.in(h_it);
-  a.d_best_inliers = st.in(h_best);
-  a.d_best_mask = st.in(h_bm);
-  a.d_best_T12 = st.in(h_bT);
-  a.d_best_R = st.in(h_bR);
-  a.d_best_t = st.in(h_bt);
-  a.d_best_s = st.in(h_bs);
-  a.d_T12 = st.out<float>(S * 16);
-  a.d_result = st.out<int>(S);
-  a.d_no_more = st.out<int>(S);
-  a.d_n_inliers = st.out<int>(S);
-  a.d_inliers = st.out<uint8_t>(S * ptp);
-  a.d_draws_consumed = st.out<int>(S);
+  a.d_iterations = st.inout(R.iterations);
+  a.d_best_inliers = st.inout(R.best_inliers);
+  a.d_best_mask = st.inout(R.best_mask);
+  a.d_best_T12 = st.inout(R.best_T12);
+  a.d_best_R = st.inout(R.best_R);
+  a.d_best_t = st.inout(R.best_t);
+  a.d_best_s = st.inout(R.best_s);
+  a.d_T12 = st.out(R.T12);
+  a.d_result = st.out(R.result);
+  a.d_no_more = st.out(R.no_more);
+  a.d_n_inliers = st.out(R.n_inliers);
+  a.d_inliers = st.out(R.inliers);
+  a.d_draws_consumed = st.out(R.draws_consumed);
   if (st.rc()) return st.rc();
   // host-pointer APIs use the null stream
   hipLaunchKernelGGL(k_sim3_iterate, dim3(nsolvers), dim3(kSim3Threads), 0, nullptr, a,
                      n_iterations, (double)RAND_MAX + 1.0);
   st.launched();
-  std::vector<int> h_res(S), h_nm(S), h_ni(S), h_dc(S);
-  std::vector<float> h_T(S * 16);
-  std::vector<uint8_t> h_inl(S * ptp);
-  st.back(h_res, a.d_result);
-  st.back(h_nm, a.d_no_more);
-  st.back(h_ni, a.d_n_inliers);
-  st.back(h_dc, a.d_draws_consumed);
-  st.back(h_T, a.d_T12);
-  st.back(h_inl, a.d_inliers);
-  st.back(h_it, a.d_iterations);
-  st.back(h_best, a.d_best_inliers);
-  st.back(h_bT, a.d_best_T12);
-  st.back(h_bR, a.d_best_R);
-  st.back(h_bt, a.d_best_t);
-  st.back(h_bs, a.d_best_s);
-  st.back(h_bm, a.d_best_mask);
+  st.back_outs();
   if (st.rc()) return st.rc();
-  for (size_t p = 0; p < S; p++) {
-    const orbsim3_problem& r = P[p];
-    *r.result = h_res[p];
-    *r.no_more = h_nm[p];
-    *r.n_inliers = h_ni[p];
-    *r.draws_consumed = h_dc[p];
-    std::copy(h_T.begin() + 16 * p, h_T.begin() + 16 * p + 16, r.T12);
-    if (r.n) std::copy(h_inl.begin() + p * ptp, h_inl.begin() + p * ptp + r.n, r.inliers);
-    if (r.n < r.min_inliers) continue;  // the early return leaves the state as it was
-    *r.iterations = h_it[p];
-    *r.best_inliers = h_best[p];
-    *r.best_s = h_bs[p];
-    std::copy(h_bT.begin() + 16 * p, h_bT.begin() + 16 * p + 16, r.best_T12);
-    std::copy(h_bR.begin() + 9 * p, h_bR.begin() + 9 * p + 9, r.best_R);
-    std::copy(h_bt.begin() + 3 * p, h_bt.begin() + 3 * p + 3, r.best_t);
-    std::copy(h_bm.begin() + p * ptp, h_bm.begin() + p * ptp + r.n, r.best_mask);
-  }
+  R.unpack();
   return ORBPL_OK;
 }
 

@@ -3,36 +3,16 @@
 // its refusals, the validation of orbsim3_iterate, its packing into the staged
 // pools and the failure path of a machine without a device, where the first
 // hipMalloc fails after the pools were packed. With a device present the
-// refusals are still checked. The library's reporters are replaced by
-// stand-ins: they are not what is under test.
-#include <cstdio>
+// refusals are still checked. orbpnp_iterate (pnp.hip) and orbkf_detect_reloc
+// (kfdb.hip) get the same failure-path block. The library's reporters are
+// check_common.h's stand-ins: they are not what is under test.
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "sim3.hip"
-
-namespace {
-std::string g_msg;
-}
-
-int orbpl::hip_fail(hipError_t e, const char* what, int line) {
-  g_msg = std::string(what) + ": " + hipGetErrorString(e);
-  (void)line;
-  return ORBPL_ERR_HIP;
-}
-int orbpl::arg_fail(const char* msg) {
-  g_msg = msg;
-  return ORBPL_ERR_ARG;
-}
-
-#define EXPECT(cond)                                                          \
-  do {                                                                        \
-    if (!(cond)) {                                                            \
-      printf("FAILED line %d: %s (last: %s)\n", __LINE__, #cond, g_msg.c_str()); \
-      return 1;                                                               \
-    }                                                                         \
-  } while (0)
+#include "pnp.hip"
+#include "kfdb.hip"
+#include "check_common.h"
 
 namespace {
 
@@ -159,6 +139,37 @@ int main() {
     EXPECT(orbsim3_iterate(two, 2, 5) == ORBPL_ERR_HIP);
     EXPECT(t.it == 0 && t.res == 7 && t.nm == 7 && t.ni == 7 && t.dc == 7 && t.inl[0] == 9);
     EXPECT(u.it == 5 && u.res == 7 && u.bs == 0);
+  }
+  {
+    // the same for orbpnp_iterate: an empty problem and one of five points
+    float p2[10] = {}, p3[15] = {}, me[5] = {}, bT[2][16] = {}, T[2][16];
+    int32_t draws[8] = {}, it[2] = {0, 0}, bi[2] = {0, 0}, out[8] = {7, 7, 7, 7, 7, 7, 7, 7};
+    uint8_t bm[5] = {}, inl[5] = {9, 9, 9, 9, 9};
+    T[0][0] = T[1][0] = 7.f;
+    orbpnp_problem two[2] = {
+        {500, 500, 320, 240, 0, nullptr, nullptr, nullptr, 4, 10, nullptr, 0, nullptr, &it[0], &bi[0],
+         nullptr, bT[0], T[0], &out[0], &out[1], &out[2], nullptr, &out[3]},
+        {500, 500, 320, 240, 5, p2, nullptr, p3, 4, 2, me, 8, draws, &it[1], &bi[1], bm, bT[1], T[1],
+         &out[4], &out[5], &out[6], inl, &out[7]}};
+    EXPECT(orbpnp_iterate(two, 2, 2) == ORBPL_ERR_HIP);
+    for (int i = 0; i < 8; i++) EXPECT(out[i] == 7);
+    EXPECT(it[0] == 0 && it[1] == 0 && bi[1] == 0 && T[0][0] == 7.f && T[1][0] == 7.f && inl[0] == 9);
+  }
+  {
+    // and for orbkf_detect_reloc: an empty database and one of two keyframes
+    const int32_t off[3] = {0, 1, 4};
+    int32_t covis[20], cand[2][64], nc[2] = {7, 7}, cw[2] = {7, 7};
+    const uint32_t words[4] = {5, 2, 6, 9}, qw[2] = {2, 9};
+    const double vals[4] = {0.5, 0.25, 0.125, 0.0625}, qv[2] = {0.75, 0.375};
+    float rs[2] = {1.5f, 2.5f};
+    for (int i = 0; i < 20; i++) covis[i] = -1;
+    cand[0][0] = cand[1][0] = 7;
+    orbkf_problem two[2] = {
+        {0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, cand[0], &nc[0], nullptr},
+        {2, off, words, vals, covis, rs, 2, qw, qv, cand[1], &nc[1], cw}};
+    EXPECT(orbkf_detect_reloc(two, 2, 0) == ORBPL_ERR_HIP);
+    EXPECT(nc[0] == 7 && nc[1] == 7 && cw[0] == 7 && cand[0][0] == 7 && cand[1][0] == 7 && rs[0] == 1.5f &&
+           rs[1] == 2.5f);
   }
   printf("sim3_check: ok\n");
   return 0;
